@@ -12,7 +12,9 @@ field is bit-identical to the CPU oracle's), inputs already resident in HBM.  Wi
 registers its own pairs (no collective on the data path); the timed region is bracketed by
 barrier + synchronize and the slowest rank's time is used: value = N*K / T (weak scaling).
 
-Extra objects on the JSON line:
+The printed line stays under 8 KB (bench_line): the contract keys, roofline, cpu_baseline, stages_ms, the mode values, the parity verdict and
+one figure per secondary config.  The whole record, every object below included, goes to --extra-out (default bench_extra.json next to
+this script).
   roofline     the SSD correlation stage (k_corr_prep + k_corr_fused of one direction, certified-fast arithmetic): algorithmic bytes
                (n^3*v*4 written + 2*C*v*4 read = 273.5 MB) / its mean duration measured with HIP events on the
                launch stream inside the timed region, against 8 TB/s HBM3E peak; `traffic` = HBM bytes per launch
@@ -22,6 +24,9 @@ Extra objects on the JSON line:
   configs      BASELINE configs[2..4] (224x192x224 masked hw 8; 32-channel nnUNet features; a slice of the two-stage sweep) timed on the same
                GPU outside the timed region of `value`, each with the roofline fraction of its correlation stage.
   batched      pairs/s with 2 / 3 / 4 pairs in flight on one GPU (cvx_register_pairs_f32), exact and fast Adam modes.
+
+--dump-outputs DIR writes the field of the last timed step (rank 0) under DIR as .npy files: a fixed, seeded sample of its voxels and
+its whole-field moments (dump_outputs).  The inputs are seeded, so two builds run with the same arguments can be compared file by file.
 """
 import argparse
 import json
@@ -51,6 +56,8 @@ TIMED_MODE_NAME = ("adam_mode=exact (the package default: MIND, correlation argm
                    "produce the reference's bits; bit-identical to oracle/cvx_oracle.c)")
 HBM_PEAK_GBS = 8000.0
 TOLERANCE_EPE = 1e-3          # north_star: mean end-point error against the reference's field, voxels
+DUMP_SAMPLE = 1 << 22         # voxels of the field written by --dump-outputs: 3 x 4 Mi x 4 B = 48 MiB (the whole field is 79 MiB)
+DUMP_SEED = 0
 
 
 def make_pair(device, idx):
@@ -342,6 +349,41 @@ def api_path(fix, mov, dev, engine_ms):
                      "165 MB / measured D2H rate + 2 x 27.5 MB / measured H2D rate")
 
 
+def dump_outputs(d, field):
+    """--dump-outputs DIR: what the timed path returned to its caller in its last step, the (3,H,W,D) float32 displacement field, as
+    DIR/displacement_sample.npy  float32 (3, DUMP_SAMPLE): the field at voxels drawn once with seed DUMP_SEED, ascending flat index;
+    DIR/displacement_moments.npy float64 (3, 2): sum and sum of squares of each component over the WHOLE field."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    flat = field.reshape(3, -1)
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(flat.shape[1], size=min(DUMP_SAMPLE, flat.shape[1]), replace=False))
+    np.save(os.path.join(d, "displacement_sample.npy"), np.ascontiguousarray(flat[:, idx], dtype=np.float32))
+    f64 = flat.astype(np.float64)
+    np.save(os.path.join(d, "displacement_moments.npy"), np.stack([f64.sum(1), (f64 * f64).sum(1)], 1))
+
+
+LINE_KEYS = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
+             "mode", "config", "roofline", "stages_ms", "cpu_baseline", "tolerance_met", "value_exact_mode", "value_fast_mode", "value_at_tolerance",
+             "value_zero_background")
+PARITY_LINE_KEYS = ("bit_identical", "epe_vs_oracle", "max_abs_diff", "tolerance_epe")
+LINE_MAX_BYTES = 8192
+
+
+def bench_line(res, extra_path=None):
+    """The printed result line: the contract keys of the full record `res`, its parity verdict and one {ms_per_pair, corr_frac} per
+    secondary config.  The whole record (every secondary figure) goes to the side file (--extra-out); a line of 24.6 KB did not parse."""
+    line = {k: res[k] for k in LINE_KEYS if k in res}
+    if "parity" in res:
+        line["parity"] = {k: res["parity"][k] for k in PARITY_LINE_KEYS if k in res["parity"]}
+    if "configs" in res:
+        line["configs"] = {name: {"ms_per_pair": c.get("ms_per_pair"), "corr_frac": (c.get("roofline_correlate") or {}).get("frac")}
+                           for name, c in res["configs"].items() if "ms_per_pair" in c}
+        if "configs[4]" in res["configs"]:
+            line["configs"]["configs[4]"] = {"items_per_s": res["configs"]["configs[4]"].get("items_per_s")}
+    line["extra"] = os.path.basename(extra_path) if extra_path else None
+    return line
+
+
 def host_cpu_model():
     try:
         for line in open("/proc/cpuinfo"):
@@ -505,7 +547,13 @@ def main():
     ap.add_argument("--no-batched", action="store_true", help="skip the secondary measurements (batched pairs, other configs, modes)")
     ap.add_argument("--adam-mode", default="exact", choices=("exact", "fast"), help="mode of the timed loop: exact = the package default (what `value` "
                     "means); fast = the opt-in throughput arithmetic of the Adam loop (profiling runs; the line then says so in `mode`)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the field of the last timed step as .npy files under DIR "
+                    "(a seeded sample of it and its whole-field moments; see dump_outputs)")
+    ap.add_argument("--extra-out", default=os.path.join(ROOT, "bench_extra.json"), metavar="FILE",
+                    help="where the whole result record goes (every secondary figure; the printed line carries the contract keys); '' = nowhere")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     global TIMED, TIMED_MODE_NAME
     if a.adam_mode == "fast":
         TIMED, TIMED_MODE_NAME = FAST, "adam_mode=fast (OPT-IN, not the package default; run with --adam-mode fast)"
@@ -557,6 +605,8 @@ def main():
     for name, ms in last_profile():
         stage_ms.setdefault(name, []).append(ms)
     set_profiling(0)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, field_of_timed_loop)
     # per-kernel durations of the Adam loop (outside the timed region): cvx_set_profiling(3) records one event behind every kernel of the loop
     kernel_ms = {}
     if rank == 0 and not a.no_batched:          # (the rocprofv3 passes of tools/profile_round.sh run with --no-batched: one pair per PMC pass)
@@ -891,7 +941,15 @@ def main():
             res["api"] = api_path(fix, mov, dev, res["ms_per_step"])
         if n == 1 and not a.no_batched:
             res["configs"] = secondary_configs(dev)
-        print(json.dumps(res))
+        extra = a.extra_out
+        if extra:
+            try:
+                with open(extra, "w") as f:
+                    f.write(json.dumps(res) + "\n")
+            except OSError as e:                                   # (a read-only checkout: the line still goes out)
+                print("bench.py: cannot write %s: %s" % (extra, e), file=sys.stderr)
+                extra = None
+        print(json.dumps(bench_line(res, extra)))
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

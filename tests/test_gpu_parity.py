@@ -996,6 +996,7 @@ def test_bench_line_with_two_ranks_on_one_gpu():
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]                       # exactly one JSON line, from rank 0
+    assert len(lines[0]) < 8192, len(lines[0])                     # short enough to be parsed (the whole record is the side file)
     b = json.loads(lines[0])
     assert b["n_gpus"] == 2 and b["steps"] == 3 and b["warmup"] == 1 and b["scaling"] == "weak" and b["unit"] == "pairs/s"
     assert abs(b["value"] - 2 * 3 / (b["ms_per_step"] * 3e-3)) < 1e-6 * b["value"]

@@ -452,3 +452,40 @@ def test_pinned_pool_marks_entries_busy_under_a_lock():
         assert all(e[1] is M._BUSY for e in pool._entries)                        # busy entries survive a clear()
     finally:
         torch.empty = real_empty
+
+
+def test_bench_line_is_short_strict_json_with_the_contract_keys():
+    """bench.py prints one line under 8 KB (a 24.6 KB line did not parse); the whole record goes to the side file.  Checked on the
+    full record of a committed bench run (profiles/r06_v4_bench_line.json, the line as it was printed before the split)."""
+    import json
+    import bench
+    with open(os.path.join(ROOT, "profiles", "r06_v4_bench_line.json")) as f:
+        res = json.loads(f.read().strip().splitlines()[-1])
+    s = json.dumps(bench.bench_line(res, "bench_extra.json"))
+    assert len(s) < bench.LINE_MAX_BYTES, len(s)
+
+    def refuse(c):
+        raise ValueError(c)
+    b = json.loads(s, parse_constant=refuse)                       # no NaN / Infinity
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "roofline", "cpu_baseline", "stages_ms", "config"):
+        assert b[k] == res[k], k
+    assert b["parity"]["bit_identical"] is True and b["extra"] == "bench_extra.json"
+    assert set(b["configs"]) == {"configs[2]", "configs[3]", "configs[4]"} and b["configs"]["configs[2]"]["corr_frac"] > 0
+
+
+def test_bench_dump_outputs_is_a_fixed_sample_under_64_mb(tmp_path):
+    """bench.py --dump-outputs: float32 / float64 .npy files, at most 64 MB in all, the same files for the same field."""
+    import bench
+    field = np.random.default_rng(3).standard_normal((3,) + bench.SHAPE).astype(np.float32)
+    bench.dump_outputs(str(tmp_path / "a"), field)
+    bench.dump_outputs(str(tmp_path / "b"), field)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["displacement_moments.npy", "displacement_sample.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= 64 << 20
+    for n in names:
+        x, y = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y)
+    s = np.load(tmp_path / "a" / "displacement_sample.npy")
+    assert s.shape == (3, bench.DUMP_SAMPLE) and np.isin(s[0, :1000], field[0]).all()
+    m = np.load(tmp_path / "a" / "displacement_moments.npy")
+    assert np.allclose(m[:, 0], field.reshape(3, -1).astype(np.float64).sum(1), rtol=0, atol=1e-6)
