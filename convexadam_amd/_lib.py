@@ -139,6 +139,11 @@ SIGNATURES = {
     "cvx_surface_distance_hist_i64": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i64, _vp, _i, _i, _vp]),
     "cvx_surface_distance_hist_bits_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "cvx_surface_distance_hist_bits_i64": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i64, _vp, _i, _i, _vp, _sz, _vp]),
+    "cvx_tps_fit_workspace_bytes": (_sz, [_i, _i]),
+    "cvx_tps_fit_f32": (_i, [_vp, _vp, _i, _i, _f, _vp, _vp, _sz, _vp]),
+    "cvx_tps_eval_f32": (_i, [_vp, _i64, _vp, _vp, _i, _i, _vp, _vp]),
+    "cvx_tps_dense_f32": (_i, [_i, _i, _i, _vp, _vp, _i, _i, _vp, _vp]),
+    "cvx_resize_trilinear_ac_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _i, _vp]),
 }
 
 _lib = None

@@ -452,3 +452,7 @@ def rescale_displacement_field(displacement_field, moving_image, fixed_image, fi
 def gpu_usage():
     print('gpu usage (current/max): {:.2f} / {:.2f} GB'.format(torch.cuda.memory_allocated() * 1e-9,
                                                                  torch.cuda.max_memory_allocated() * 1e-9))
+
+
+# thin-plate-spline densification (l2r_2021_convexAdam_task1_docker.py:198-262,365-387): csrc/tps.hip
+from .tps import TPS, thin_plate_dense, tps_densify  # noqa: E402,F401

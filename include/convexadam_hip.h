@@ -503,6 +503,26 @@ int cvx_surface_distance_hist_bits_i64(const uint64_t* bits_b, const uint64_t* b
                                        const uint64_t* active4, int nbins, int64_t* hist, int64_t hist_stride, int* overflow,
                                        int overflow_stride, int max_radius, void* workspace, size_t workspace_bytes, void* stream);
 
+/* thin-plate-spline densification (csrc/tps.hip) ---------------------------------------------------------------------------------
+ * replaces TPS.fit / TPS.z / thin_plate_dense and the align_corners=True up-sampling of     l2r_2021_convexAdam_task1_docker.py:198-262
+ *   centres [n][3] (x, y, z normalised coordinates as F.affine_grid writes them), values [n][nrhs], theta [n+4][nrhs] (rows 0..n-1 = w,
+ *   n..n+3 = a0..a3, the layout of the reference's theta), 1 <= n <= 16384, 1 <= nrhs <= 4.  U(r) = r^2 log(r + 1e-6) with r^2 from direct
+ *   coordinate differences (csrc/tps.hip explains why).
+ * cvx_tps_fit_f32      : TPS.fit(c, f, lambd) (task1:200-222): assembles [K + lambda I, P; P^T, 0] theta = [f; 0] in the workspace and
+ *                        solves it by blocked LU with partial pivoting.  SYNCHRONISES `stream` (it reads the pivot status back): a zero
+ *                        or non-finite pivot returns CVX_ERR_INVALID_ARG "singular system" and leaves theta unwritten */
+size_t cvx_tps_fit_workspace_bytes(int n, int nrhs);
+int cvx_tps_fit_f32(const float* centres, const float* values, int n, int nrhs, float lambd, float* theta, void* workspace,
+                    size_t workspace_bytes, void* stream);
+/* cvx_tps_eval_f32     : TPS.z(x, c, theta) (task1:233-239) at m points [m][3] -> out [m][nrhs] */
+int cvx_tps_eval_f32(const float* points, int64_t m, const float* centres, const float* theta, int n, int nrhs, float* out, void* stream);
+/* cvx_tps_dense_f32    : the same at the F.affine_grid(eye, (1,1,s0,s1,s2), align_corners=True) lattice, generated in the kernel
+ *                        (thin_plate_dense, task1:247-257; x runs along s2, z along s0) -> out [nrhs][s0][s1][s2] */
+int cvx_tps_dense_f32(int s0, int s1, int s2, const float* centres, const float* theta, int n, int nrhs, float* out, void* stream);
+/* F.interpolate(x, size, mode='trilinear', align_corners=True)            task1:260
+ *   in [C][h][w][d] -> out [C][H][W][D]; bit-identical to ATen's CPU kernel in float32 */
+int cvx_resize_trilinear_ac_f32(const float* in, int C, int h, int w, int d, float* out, int H, int W, int D, void* stream);
+
 #pragma GCC visibility pop
 
 #ifdef __cplusplus
