@@ -11,11 +11,31 @@ from ._lib import check, f32c, lib, ptr, require_device_tensor, stream_ptr, work
 _MAX_RHS = 4
 
 
+def _shape(t, name):
+    """The shape of a tensor, read from its metadata only (the checks below answer before any device is touched)."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("%s must be a torch.Tensor" % name)
+    return tuple(int(s) for s in t.shape)
+
+
+def _centres(c, name="c"):
+    """n of a (n, 3) centre array, n >= 1."""
+    s = _shape(c, name)
+    if len(s) != 2 or s[1] != 3 or s[0] < 1:
+        raise ValueError("%s must be (n, 3) with n >= 1, got %s" % (name, s))
+    return s[0]
+
+
+def _theta(theta, n):
+    s = _shape(theta, "theta")
+    if len(s) != 2 or s[0] != n + 4 or s[1] < 1:
+        raise ValueError("theta must be (n+4, f_dim) with n = %d and f_dim >= 1, got %s" % (n, s))
+
+
 def _columns(t, name):
-    """(k, d) float32 device tensor -> list of contiguous (k, <=4) column groups (the library takes at most 4 right-hand sides)."""
+    """(k, d) float32 device tensor, shape already checked -> list of contiguous (k, <=4) column groups (the library takes at most 4
+    right-hand sides)."""
     t = f32c(require_device_tensor(t, name))
-    if t.dim() != 2:
-        raise ValueError("%s must be 2-D, got shape %s" % (name, tuple(t.shape)))
     return [t[:, i:i + _MAX_RHS].contiguous() for i in range(0, t.shape[1], _MAX_RHS)]
 
 
@@ -24,12 +44,11 @@ class TPS:
     def fit(c, f, lambd=0.):
         """theta (n+4, f_dim) of the spline through f at the centres c (n, 3): solves [U(d(c,c)) + lambd I, P; P^T, 0] theta = [f; 0]
         (task1:200-222).  Raises CvxError ("singular system") on a zero or non-finite pivot, e.g. duplicate centres with lambd = 0."""
+        n = _centres(c)
+        fs = _shape(f, "f")
+        if len(fs) != 2 or fs[0] != n or fs[1] < 1:
+            raise ValueError("f must be (n, f_dim) with n = %d and f_dim >= 1, got %s" % (n, fs))
         c = f32c(require_device_tensor(c, "c"))
-        n = int(c.shape[0])
-        if c.dim() != 2 or c.shape[1] != 3:
-            raise ValueError("c must be (n, 3), got %s" % (tuple(c.shape),))
-        if f.dim() != 2 or int(f.shape[0]) != n:
-            raise ValueError("f must be (n, f_dim) with n = %d, got %s" % (n, tuple(f.shape)))
         parts = []
         with torch.cuda.device(c.device):
             for fk in _columns(f, "f"):
@@ -58,11 +77,13 @@ class TPS:
     @staticmethod
     def z(x, c, theta):
         """Spline value (m, f_dim) at the points x (m, 3) (task1:236-241)."""
+        xs = _shape(x, "x")
+        if len(xs) != 2 or xs[1] != 3:
+            raise ValueError("x must be (m, 3), got %s" % (xs,))
+        n, m = _centres(c), xs[0]
+        _theta(theta, n)
         x = f32c(require_device_tensor(x, "x"))
         c = f32c(require_device_tensor(c, "c"))
-        n, m = int(c.shape[0]), int(x.shape[0])
-        if theta.dim() != 2 or int(theta.shape[0]) != n + 4:
-            raise ValueError("theta must be (n+4, f_dim) with n = %d, got %s" % (n, tuple(theta.shape)))
         parts = []
         with torch.cuda.device(x.device):
             for th in _columns(theta, "theta"):
@@ -75,9 +96,15 @@ class TPS:
 
 def tps_dense(c, theta, size):
     """The spline at the F.affine_grid(eye, (1,1)+size, align_corners=True) lattice, generated in the kernel: (f_dim,) + size."""
+    n = _centres(c)
+    _theta(theta, n)
+    try:
+        s0, s1, s2 = [int(s) for s in size]
+    except (TypeError, ValueError):
+        raise ValueError("size must be three positive ints, got %r" % (size,)) from None
+    if min(s0, s1, s2) < 1:
+        raise ValueError("size must be three positive ints, got %r" % (size,))
     c = f32c(require_device_tensor(c, "c"))
-    n = int(c.shape[0])
-    s0, s1, s2 = [int(s) for s in size]
     parts = []
     with torch.cuda.device(c.device):
         for th in _columns(theta, "theta"):
@@ -89,14 +116,17 @@ def tps_dense(c, theta, size):
 
 
 def resize_trilinear_ac(x, size):
-    """F.interpolate(x, size=size, mode='trilinear', align_corners=True) for (1,C,h,w,d) (task1:260)."""
-    x = require_device_tensor(x, "x")
-    _, Cn, h, w, d = [int(s) for s in x.shape]
+    """F.interpolate(x, size=size, mode='trilinear', align_corners=True) for (N,C,h,w,d) (task1:260).  The contiguous (N, C, h, w, d)
+    input is the (1, N*C, h, w, d) one, so the batch rides along as channels."""
+    xs = _shape(x, "x")
+    if len(xs) != 5:
+        raise ValueError("x must be (N, C, h, w, d), got %s" % (xs,))
+    Nb, Cn, h, w, d = xs
     H, W, D = [int(s) for s in size]
-    a = f32c(x)
-    out = torch.empty((1, Cn, H, W, D), dtype=torch.float32, device=a.device)
+    a = f32c(require_device_tensor(x, "x"))
+    out = torch.empty((Nb, Cn, H, W, D), dtype=torch.float32, device=a.device)
     with torch.cuda.device(a.device):
-        check(lib().cvx_resize_trilinear_ac_f32(ptr(a), Cn, h, w, d, ptr(out), H, W, D, stream_ptr(a.device)))
+        check(lib().cvx_resize_trilinear_ac_f32(ptr(a), Nb * Cn, h, w, d, ptr(out), H, W, D, stream_ptr(a.device)))
     return out
 
 

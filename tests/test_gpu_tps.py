@@ -115,11 +115,12 @@ def masked_centres(n, seed, size=(32, 32, 32)):
     return pts[torch.randperm(pts.shape[0], generator=g)[:n]].contiguous()
 
 
-def smooth_values(c, seed):
+def smooth_values(c, seed, k=3):
+    """(n, k) smooth values plus noise (k = 3 draws what it always drew)."""
     g = torch.Generator().manual_seed(seed)
-    a = torch.rand(3, 3, generator=g) * 3 + 1
-    f = torch.stack([sum(0.02 * torch.sin(a[k, i] * c[:, i] + k) for i in range(3)) for k in range(3)], 1)
-    return (f + 0.002 * torch.randn(c.shape[0], 3, generator=g)).contiguous()
+    a = torch.rand(k, 3, generator=g) * 3 + 1
+    f = torch.stack([sum(0.02 * torch.sin(a[j, i] * c[:, i] + j) for i in range(3)) for j in range(k)], 1)
+    return (f + 0.002 * torch.randn(c.shape[0], k, generator=g)).contiguous()
 
 
 def assert_no_worse(hip, ref32, exact, fmax, what):
@@ -160,18 +161,24 @@ def test_dense_lattice_matches_restatement(size):
 
 
 # ---- 2. fit ----------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("lambd", [0.0, 0.1])
-@pytest.mark.parametrize("n", [5, 17, 64, 300, 1000, 4096])
-def test_fit_backward_error_and_values(n, lambd):
-    from convexadam_amd.convex_adam_utils import TPS
-    c = masked_centres(n, seed=n)
-    f = smooth_values(c, seed=n + 1)
-    theta = TPS.fit(c.to(DEV), f.to(DEV), lambd)
+def backward_error_ok(c, f, lambd, theta):
+    """theta finite and the normwise backward error on the float64 system <= 4 (n+4) u; returns theta as float64."""
+    n = c.shape[0]
     th = theta.cpu().numpy().astype(np.float64)
     assert np.isfinite(th).all()
     A, v = system64(c.numpy(), f.numpy(), lambd)
     be = np.abs(A @ th - v).max() / (np.abs(A).sum(1).max() * np.abs(th).max())
     assert be <= 4 * (n + 4) * U32, "backward error %.3g > %.3g" % (be, 4 * (n + 4) * U32)
+    return th
+
+
+def check_fit(c, f, lambd):
+    """The fit criteria of the header: backward error, values at the centres and on a lattice against the float32 reference."""
+    from convexadam_amd.convex_adam_utils import TPS
+    n = c.shape[0]
+    theta = TPS.fit(c.to(DEV), f.to(DEV), lambd)
+    assert theta.shape == (n + 4, f.shape[1])
+    backward_error_ok(c, f, lambd, theta)
     t64 = fit64(c.numpy(), f.numpy(), lambd)
     t32 = fit32(c, f, lambd)
     fmax = float(np.abs(f.numpy()).max())
@@ -180,6 +187,14 @@ def test_fit_backward_error_and_values(n, lambd):
     x = lattice((11, 12, 10))
     assert_no_worse(TPS.z(x.to(DEV), c.to(DEV), theta).cpu().numpy(), z32(x, c, t32).numpy(), z64(x.numpy(), c.numpy(), t64), fmax,
                     "values on a lattice")
+    return theta
+
+
+@pytest.mark.parametrize("lambd", [0.0, 0.1])
+@pytest.mark.parametrize("n", [5, 17, 64, 300, 1000, 4096])
+def test_fit_backward_error_and_values(n, lambd):
+    c = masked_centres(n, seed=n)
+    check_fit(c, smooth_values(c, seed=n + 1), lambd)
 
 
 # ---- 3. known answer: an affine f is reproduced -------------------------------------------------------------------------------------
@@ -300,3 +315,277 @@ def test_duplicate_centres_raise_and_write_nothing():
     theta = TPS.fit(cd, fd, 0.1)
     assert torch.isfinite(theta).all()
     torch.cuda.synchronize()
+
+
+# ---- 8. exact invariants (the build has no contraction and no atomics in the arithmetic: these hold bit for bit) -----------------
+F_DIMS = [1, 2, 3, 4, 5, 8]           # every k_tps_eval<NR> instantiation, and the groups of 4 plus a remainder of tps._columns
+
+
+@pytest.mark.parametrize("n", [70, 125])  # N = 74: three panels, a GEMM, two back-substitution blocks; N = 129: a last block of 1 row
+def test_fit_columns_are_independent(n):
+    """The pivots depend only on the matrix columns, and every right-hand side goes through the same swaps, triangular solve, GEMM
+    element and back substitution in the same order, whatever its neighbours."""
+    from convexadam_amd.convex_adam_utils import TPS
+    c = masked_centres(n, seed=21).to(DEV)
+    f = smooth_values(c.cpu(), seed=22, k=max(F_DIMS)).to(DEV)
+    single = [TPS.fit(c, f[:, k:k + 1]) for k in range(f.shape[1])]
+    for fd in F_DIMS:
+        theta = TPS.fit(c, f[:, :fd])
+        assert theta.shape == (n + 4, fd)
+        for k in range(fd):
+            assert torch.equal(theta[:, k], single[k][:, 0]), "f_dim %d, column %d" % (fd, k)
+
+
+def test_nan_in_one_value_column_poisons_only_that_column():
+    from convexadam_amd.convex_adam_utils import TPS
+    c = masked_centres(100, seed=23).to(DEV)
+    f = smooth_values(c.cpu(), seed=24, k=5).to(DEV)
+    clean = TPS.fit(c, f)
+    f[37, 1] = float("nan")
+    theta = TPS.fit(c, f)                                    # the pivots never look at the right-hand sides: no error
+    assert torch.isnan(theta[:, 1]).all()
+    for k in (0, 2, 3, 4):
+        assert torch.equal(theta[:, k], clean[:, k]), "column %d" % k
+
+
+def test_eval_columns_are_independent_and_bounded():
+    from convexadam_amd.convex_adam_utils import TPS
+    n, m = 300, 1500
+    g = torch.Generator().manual_seed(25)
+    c = torch.rand(n, 3, generator=g) * 2 - 1
+    x = torch.rand(m, 3, generator=g) * 2.2 - 1.1
+    x[:5] = c[:5]
+    theta = torch.randn(n + 4, max(F_DIMS), generator=g) * 0.1
+    xd, cd, td = x.to(DEV), c.to(DEV), theta.to(DEV)
+    single = [TPS.z(xd, cd, td[:, k:k + 1]) for k in range(theta.shape[1])]
+    for fd in F_DIMS:
+        out = TPS.z(xd, cd, td[:, :fd])
+        assert out.shape == (m, fd)
+        for k in range(fd):
+            assert torch.equal(out[:, k], single[k][:, 0]), "f_dim %d, column %d" % (fd, k)
+        err = np.abs(out.cpu().numpy() - z64(x.numpy(), c.numpy(), theta[:, :fd].numpy()))
+        assert np.all(err <= eval_bound(x.numpy(), c.numpy(), theta[:, :fd].numpy())), "f_dim %d" % fd
+
+
+@pytest.mark.parametrize("size", [(40, 48, 56), (37, 41, 29), (2, 3, 2), (1, 6, 5), (5, 1, 1), (1, 1, 1)])
+def test_dense_lattice_is_the_evaluated_lattice(size):
+    """tps_dense generates torch's float32 affine_grid lattice in the kernel: every bit of it, so the same spline values."""
+    from convexadam_amd.convex_adam_utils import TPS
+    from convexadam_amd.tps import tps_dense
+    n, fd = 300, 5
+    g = torch.Generator().manual_seed(26)
+    c = (torch.rand(n, 3, generator=g) * 2 - 1).to(DEV)
+    theta = (torch.randn(n + 4, fd, generator=g) * 0.1).to(DEV)
+    out = tps_dense(c, theta, size)
+    assert out.shape == (fd,) + size
+    ref = TPS.z(lattice(size).to(DEV), c, theta)
+    assert torch.equal(out, ref.t().reshape((fd,) + size))
+
+
+def _abi_fit(c, f, lambd, theta, ws):
+    from convexadam_amd import _lib
+    L = _lib.lib()
+    n, nr = int(c.shape[0]), int(f.shape[1])
+    rc = L.cvx_tps_fit_f32(_lib.ptr(c), _lib.ptr(f), n, nr, float(lambd), _lib.ptr(theta), _lib.ptr(ws), int(ws.numel()), _lib.stream_ptr())
+    torch.cuda.synchronize()
+    return rc, L.cvx_last_error()
+
+
+def test_fit_is_deterministic_and_ignores_the_workspace_contents():
+    from convexadam_amd import _lib
+    n = 200
+    c = masked_centres(n, seed=27).to(DEV)
+    f = smooth_values(c.cpu(), seed=28).to(DEV)
+    nws = _lib.lib().cvx_tps_fit_workspace_bytes(n, 3)
+
+    def fit(ws):
+        theta = torch.zeros(n + 4, 3, device=DEV)
+        rc, msg = _abi_fit(c, f, 0.0, theta, ws)
+        assert rc == _lib.CVX_OK, msg
+        return theta
+
+    a = fit(torch.zeros(nws, dtype=torch.uint8, device=DEV))
+    assert torch.equal(a, fit(torch.zeros(nws, dtype=torch.uint8, device=DEV)))
+    assert torch.equal(a, fit(torch.full((nws,), 0xFF, dtype=torch.uint8, device=DEV)))
+    # a fit that stops at a singular pivot leaves its workspace half factorised; the next fit in it does not see that
+    ws = torch.zeros(nws, dtype=torch.uint8, device=DEV)
+    cz = c.clone()
+    cz[:, 2] = 0.0
+    rc, msg = _abi_fit(cz, f, 0.0, torch.zeros(n + 4, 3, device=DEV), ws)
+    assert rc == _lib.CVX_ERR_INVALID_ARG and b"singular" in msg
+    assert torch.equal(a, fit(ws))
+
+
+# ---- 9. batched and wide resize -----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("nc", [(2, 3), (3, 1), (2, 4)])
+def test_resize_batched_bit_identical(nc):
+    from convexadam_amd.tps import resize_trilinear_ac
+    g = torch.Generator().manual_seed(30 + sum(nc))
+    x = torch.randn(*nc, 5, 6, 7, generator=g)
+    ref = F.interpolate(x, (9, 11, 13), mode="trilinear", align_corners=True)
+    out = resize_trilinear_ac(x.to(DEV), (9, 11, 13)).cpu()
+    assert out.shape == ref.shape
+    assert np.array_equal(out.numpy(), ref.numpy())
+
+
+@pytest.mark.parametrize("D", [257, 300])                    # D > 256: several x-blocks at the widest block size
+@pytest.mark.parametrize("C", [1, 4, 7])
+def test_resize_wide_rows_bit_identical(C, D):
+    from convexadam_amd.tps import resize_trilinear_ac
+    g = torch.Generator().manual_seed(C * D)
+    x = torch.randn(1, C, 3, 4, 9, generator=g)
+    ref = F.interpolate(x, (5, 6, D), mode="trilinear", align_corners=True)
+    assert np.array_equal(resize_trilinear_ac(x.to(DEV), (5, 6, D)).cpu().numpy(), ref.numpy())
+
+
+def test_resize_refuses_an_output_beyond_the_grid_limit():
+    from convexadam_amd import _lib
+    from convexadam_amd.tps import resize_trilinear_ac
+    x = torch.rand(1, 1, 2, 2, 2, device=DEV)
+    with pytest.raises(_lib.CvxError, match="grid limits"):
+        resize_trilinear_ac(x, (65536, 1, 1))                 # refused on the host: a 256 KB output, nothing launched
+    torch.cuda.synchronize()
+
+
+# ---- 10. LU block edges and evaluation chunk edges against the float64 restatement -----------------------------------------------
+NB = 32                               # panel width of the LU (csrc/tps.hip); the GEMM tiles are 64 x 64, the back substitution 64 rows
+LU_EDGE_N = [27, 28, 29, 60, 61, 91, 124, 1020, 1021, 2045]     # N = n + 4 = 31, 32, 33, 64, 65, 95, 128, 1024, 1025, 2049
+LU_EDGES = [(n, fd) for n in LU_EDGE_N for fd in (1, 4)] + [(29, 2), (61, 2)]
+
+
+def _lu_launches(N, nrhs):
+    """(nb, right, rows) of every panel step of cvx_tps_fit_f32: GEMM launched iff rows > 0, `right` columns wide."""
+    ncol = N + nrhs
+    return [(min(NB, N - k0), ncol - k0 - min(NB, N - k0), N - k0 - min(NB, N - k0)) for k0 in range(0, N, NB)]
+
+
+def test_lu_edge_cases_sit_on_the_block_edges():
+    Ns = {n + 4 for n, _ in LU_EDGES}
+    for r in (0, 1):
+        assert any(N % NB == r for N in Ns) and any(N % 64 == r for N in Ns)   # full / 1-column last panel, 64 / 1-row backsub block
+    assert {1024, 1025} <= Ns                                                  # the 1024-thread panel loop wraps
+    assert (27, 1) in LU_EDGES and (27 + 5) % NB == 0                        # ncol = N + nrhs at 0 and 1 mod 32
+    assert (28, 1) in LU_EDGES and (28 + 5) % NB == 1
+    steps = [s for n, fd in LU_EDGES for s in _lu_launches(n + 4, fd)]
+    assert any(rows == 1 for _, _, rows in steps)                              # the 1-row trailing GEMM
+    for r in (0, 1):                                                           # GEMM width on, and one past, its 64-column tile edge
+        assert any(rows > 0 and right % 64 == r for _, right, rows in steps)
+
+
+@pytest.mark.parametrize("lambd", [0.0, 0.1])
+@pytest.mark.parametrize("n,fd", LU_EDGES)
+def test_fit_lu_block_edges(n, fd, lambd):
+    c = masked_centres(n, seed=100 + n)
+    check_fit(c, smooth_values(c, seed=200 + n, k=fd), lambd)
+
+
+EVAL_M = [1, 255, 256, 257, 511, 512, 513, 1025]
+
+
+@pytest.mark.parametrize("fd", [1, 2, 4])
+@pytest.mark.parametrize("n", [255, 256, 257, 511, 512, 513])   # centres staged 256 at a time
+def test_eval_chunk_edges(n, fd):
+    """m at the edges of the 512-point blocks: the full evaluation is graded, every shorter prefix must equal its head bit for bit."""
+    from convexadam_amd.convex_adam_utils import TPS
+    g = torch.Generator().manual_seed(300 + n)
+    c = torch.rand(n, 3, generator=g) * 2 - 1
+    x = torch.rand(max(EVAL_M), 3, generator=g) * 2.2 - 1.1
+    for i, j in ((0, 0), (255, 255), (256, n - 1), (511, 256), (512, n // 2), (1024, n - 256)):
+        x[i] = c[j % n]                                        # points on centres (r = 0), at the block edges, from either chunk
+    theta = torch.randn(n + 4, fd, generator=g) * 0.1
+    xd, cd, td = x.to(DEV), c.to(DEV), theta.to(DEV)
+    full = TPS.z(xd, cd, td)
+    err = np.abs(full.cpu().numpy() - z64(x.numpy(), c.numpy(), theta.numpy()))
+    assert np.all(err <= eval_bound(x.numpy(), c.numpy(), theta.numpy())), "max err/bound %.3g" % float(
+        (err / eval_bound(x.numpy(), c.numpy(), theta.numpy())).max())
+    for m in EVAL_M[:-1]:
+        assert torch.equal(TPS.z(xd[:m], cd, td), full[:m]), "m = %d" % m
+
+
+# ---- 11. ill-conditioned but regular, and the affine known answer for every lambda -------------------------------------------------
+def test_fit_close_partner_centres():
+    """lambda = 0, 500 masked centres, 100 with a partner at 1e-3 and 20 with one at 2e-5 (distinct in float32): a regular system
+    with tiny pivots; the backward error keeps its bound."""
+    from convexadam_amd.convex_adam_utils import TPS
+    base = masked_centres(500, seed=31)
+    g = torch.Generator().manual_seed(32)
+    d = torch.randn(120, 3, generator=g)
+    d = d / d.norm(dim=1, keepdim=True)
+    dist = torch.cat([torch.full((100, 1), 1e-3), torch.full((20, 1), 2e-5)])
+    c = torch.cat([base, base[:120] + dist * d]).contiguous()
+    assert (c[500:] != base[:120]).any(1).all()
+    f = smooth_values(c, seed=33)
+    backward_error_ok(c, f, 0.0, TPS.fit(c.to(DEV), f.to(DEV), 0.0))
+
+
+@pytest.mark.parametrize("lambd", [0.0, 0.1, 10.0])
+def test_affine_known_answer_every_lambda(lambd):
+    """f = c M + b exactly (dyadic centres on the 33^3 lattice, M and b in 1/64ths): the solution is w = 0 and affine rows (b, M) for
+    every lambda.  Values on a lattice, the weights and the affine rows are graded against the float32 reference."""
+    from convexadam_amd.convex_adam_utils import TPS
+    n = 500
+    c = masked_centres(n, seed=34, size=(33, 33, 33))
+    M = torch.tensor([[2.0, -1.0, 1.0], [1.0, 3.0, -1.0], [-3.0, 1.0, 1.0]]) / 64
+    b = torch.tensor([1.0, -1.0, 2.0]) / 64
+    f = (c @ M + b).contiguous()
+    assert torch.equal(f.double(), c.double() @ M.double() + b.double())
+    theta = TPS.fit(c.to(DEV), f.to(DEV), lambd)
+    th = theta.cpu().numpy()
+    t32 = fit32(c, f, lambd)
+    fmax = float(np.abs(f.numpy()).max())
+    x = lattice((11, 12, 10))
+    exact = x.double().numpy() @ M.double().numpy() + b.double().numpy()
+    assert_no_worse(TPS.z(x.to(DEV), c.to(DEV), theta).cpu().numpy(), z32(x, c, t32).numpy(), exact, fmax, "values on a lattice")
+    assert_no_worse(th[:n], t32[:n].numpy(), 0.0, fmax, "weights")
+    assert_no_worse(th[n:], t32[n:].numpy(), np.concatenate([b[None].double().numpy(), M.double().numpy()]), fmax, "affine rows")
+
+
+# ---- 12. error paths: zero and non-finite pivots ---------------------------------------------------------------------------------
+def _check_refused_then_recovers(c, f, lambd, what):
+    """Through the ABI: the fit refuses with `what` in the message and leaves theta as it was; the next good fit in the same
+    workspace gives what a fresh workspace gives."""
+    from convexadam_amd import _lib
+    n = int(c.shape[0])
+    nws = _lib.lib().cvx_tps_fit_workspace_bytes(n, 3)
+    ws = torch.zeros(nws, dtype=torch.uint8, device=DEV)
+    sentinel = torch.arange((n + 4) * 3, dtype=torch.float32, device=DEV).view(n + 4, 3)
+    theta = sentinel.clone()
+    rc, msg = _abi_fit(c.to(DEV), f.to(DEV), lambd, theta, ws)
+    assert rc == _lib.CVX_ERR_INVALID_ARG and what in msg, msg
+    assert torch.equal(theta, sentinel)
+    good = masked_centres(n, seed=40).to(DEV)
+    fg = smooth_values(good.cpu(), seed=41).to(DEV)
+    fresh = torch.zeros(n + 4, 3, device=DEV)
+    assert _abi_fit(good, fg, lambd, fresh, torch.zeros(nws, dtype=torch.uint8, device=DEV))[0] == _lib.CVX_OK
+    theta = torch.zeros(n + 4, 3, device=DEV)
+    assert _abi_fit(good, fg, lambd, theta, ws)[0] == _lib.CVX_OK
+    assert torch.equal(theta, fresh)
+
+
+@pytest.mark.parametrize("lambd", [0.0, 0.1])
+def test_planar_centres_give_a_zero_pivot(lambd):
+    """All centres at z = 0.0: row and column n+3 of the system are exactly zero through every update, so column n+3 has a zero pivot
+    (not the coincident-centre path: the centres are distinct)."""
+    from convexadam_amd import _lib
+    from convexadam_amd.convex_adam_utils import TPS
+    n = 60
+    g = torch.Generator().manual_seed(42)
+    c = torch.rand(n, 3, generator=g) * 2 - 1
+    c[:, 2] = 0.0
+    f = smooth_values(c, seed=43)
+    with pytest.raises(_lib.CvxError, match="zero or non-finite pivot in column %d of %d" % (n + 3, n + 4)):
+        TPS.fit(c.to(DEV), f.to(DEV), lambd)
+    _check_refused_then_recovers(c, f, lambd, b"zero or non-finite pivot")
+
+
+@pytest.mark.parametrize("bad", [float("nan"), float("inf")])
+def test_non_finite_centre_gives_a_non_finite_pivot(bad):
+    from convexadam_amd import _lib
+    from convexadam_amd.convex_adam_utils import TPS
+    n = 60
+    c = masked_centres(n, seed=44)
+    f = smooth_values(c, seed=45)
+    c[7, 1] = bad
+    with pytest.raises(_lib.CvxError, match="zero or non-finite pivot"):
+        TPS.fit(c.to(DEV), f.to(DEV), 0.0)
+    _check_refused_then_recovers(c, f, 0.0, b"zero or non-finite pivot")

@@ -80,3 +80,66 @@ def test_python_layer_has_no_cpu_path():
         TPS.fit(c, torch.rand(8, 3))
     with pytest.raises(RuntimeError, match="no CPU path"):
         thin_plate_dense(c.unsqueeze(0), torch.rand(1, 8, 3), (8, 8, 8), 2)
+
+
+# ---- shape validation in tps.py: answered from tensor metadata before the device check, so CPU tensors with bad shapes raise ValueError
+def _fit(c, f):
+    from convexadam_amd.tps import TPS
+    return TPS.fit(c, f)
+
+
+def _z(x, c, theta):
+    from convexadam_amd.tps import TPS
+    return TPS.z(x, c, theta)
+
+
+def _dense(c, theta, size):
+    from convexadam_amd.tps import tps_dense
+    return tps_dense(c, theta, size)
+
+
+def _resize(x, size):
+    from convexadam_amd.tps import resize_trilinear_ac
+    return resize_trilinear_ac(x, size)
+
+
+R = torch.rand
+BAD_SHAPES = {
+    "fit_c_no_centres": lambda: _fit(R(0, 3), R(0, 3)),
+    "fit_c_two_coords": lambda: _fit(R(8, 2), R(8, 3)),
+    "fit_c_1d": lambda: _fit(R(24), R(8, 3)),
+    "fit_f_rows": lambda: _fit(R(8, 3), R(7, 3)),
+    "fit_f_no_columns": lambda: _fit(R(8, 3), R(8, 0)),
+    "fit_f_1d": lambda: _fit(R(8, 3), R(8)),
+    "z_x_two_coords": lambda: _z(R(10, 2), R(8, 3), R(12, 3)),
+    "z_x_1d": lambda: _z(R(30), R(8, 3), R(12, 3)),
+    "z_c_two_coords": lambda: _z(R(10, 3), R(8, 2), R(12, 3)),
+    "z_c_no_centres": lambda: _z(R(10, 3), R(0, 3), R(4, 3)),
+    "z_theta_no_affine_rows": lambda: _z(R(10, 3), R(8, 3), R(8, 3)),
+    "z_theta_no_columns": lambda: _z(R(10, 3), R(8, 3), R(12, 0)),
+    "z_theta_1d": lambda: _z(R(10, 3), R(8, 3), R(12)),
+    "dense_c_two_coords": lambda: _dense(R(8, 2), R(12, 3), (4, 4, 4)),
+    "dense_theta_no_affine_rows": lambda: _dense(R(8, 3), R(8, 3), (4, 4, 4)),
+    "dense_theta_no_columns": lambda: _dense(R(8, 3), R(12, 0), (4, 4, 4)),
+    "dense_size_two_ints": lambda: _dense(R(8, 3), R(12, 3), (4, 4)),
+    "dense_size_zero": lambda: _dense(R(8, 3), R(12, 3), (4, 0, 4)),
+    "dense_size_negative": lambda: _dense(R(8, 3), R(12, 3), (4, 4, -2)),
+    "dense_size_not_a_sequence": lambda: _dense(R(8, 3), R(12, 3), 4),
+    "resize_x_4d": lambda: _resize(R(3, 4, 4, 4), (8, 8, 8)),
+    "resize_x_6d": lambda: _resize(R(1, 1, 3, 4, 4, 4), (8, 8, 8)),
+}
+
+
+@pytest.mark.parametrize("case", sorted(BAD_SHAPES))
+def test_bad_shapes_raise_value_error_before_the_device_check(case):
+    with pytest.raises(ValueError):
+        BAD_SHAPES[case]()
+
+
+def test_valid_shapes_on_cpu_still_reach_the_device_check():
+    from convexadam_amd.tps import TPS, resize_trilinear_ac, tps_dense
+    c = torch.rand(8, 3)
+    for call in (lambda: TPS.fit(c, torch.rand(8, 5)), lambda: TPS.z(torch.rand(10, 3), c, torch.rand(12, 2)),
+                 lambda: tps_dense(c, torch.rand(12, 1), (4, 5, 6)), lambda: resize_trilinear_ac(torch.rand(2, 3, 4, 4, 4), (8, 8, 8))):
+        with pytest.raises(RuntimeError, match="no CPU path"):
+            call()
