@@ -158,15 +158,25 @@ __global__ __launch_bounds__(256) void k_adam_update(const float* __restrict__ G
     v[i] = vv;
 }
 
+// the k_box3_tile variant (>= 1000) that runs this three-box pass, or 0 (z-marching pipeline / k_box3x3).  adam_run_impl asks it once per
+// iteration for the adjoint, so that the warp kernel pre-divides gU exactly when the tiles take it pre-divided.
+static int box3_tile_choice(const float* in, const float* out, int h, int w, int d, bool backward, const float* P, const float* m, const float* v,
+                            const float* gsave) {
+    if (options().box_tiled != 0) return 0;
+    if (!(backward ? (out || P) && box3_tile_supported(in, out, h, w, d, P, m, v, gsave) : box3_tile_fwd_supported(in, out, h, w, d))) return 0;
+    long long ft = backward ? options().box_bwd_tile : options().box_fwd_tile;
+    if (ft < 0) ft = box3_march_supported(d) ? box3_tile_fwd_auto(h, w, d) : 2000;          // (rows beyond the marching kernel's range: always tiles)
+    return ft >= 1000 ? (int)ft : 0;
+}
+
+// prediv: the adjoint's input is gU / 27 already -- only the tiles take it so (the caller decides with box3_tile_choice)
 static int launch_box3x3(const float* in, float* out, int h, int w, int d, bool backward, float* P, float* m, float* v,
-                         AdamConsts ac, float* gsave, hipStream_t s) {
+                         AdamConsts ac, float* gsave, bool prediv, hipStream_t s) {
     // rows of up to 126 voxels: z-marching pipeline (boxmarch.hip); longer rows: the tiled kernel below
+    const int ft = box3_tile_choice(in, out, h, w, d, backward, P, m, v, gsave);
+    if (ft) return launch_box3_tile(in, out, h, w, d, ft, backward, P, m, v, ac, gsave, prediv, s);
+    if (prediv) return fail(CVX_ERR_INVALID_ARG, "box3x3: pre-divided adjoint taps without the tile kernel");
     const bool force_tiled = options().box_tiled != 0;
-    if (!force_tiled && (backward ? (out || P) && box3_tile_supported(in, out, h, w, d, P, m, v, gsave) : box3_tile_fwd_supported(in, out, h, w, d))) {
-        long long ft = backward ? options().box_bwd_tile : options().box_fwd_tile;
-        if (ft < 0) ft = box3_march_supported(d) ? box3_tile_fwd_auto(h, w, d) : 2000;      // (rows beyond the marching kernel's range: always tiles)
-        if (ft >= 1000) return launch_box3_tile(in, out, h, w, d, (int)ft, backward, P, m, v, ac, gsave, s);
-    }
     if (!force_tiled && box3_march_supported(d)) return launch_box3_march(in, out, h, w, d, backward, P, m, v, ac, gsave, s);
     const int nb = cdiv(d, BT_X) * cdiv(w, BT_Y) * cdiv(h, BT_Z) * 3;
     if (!backward) hipLaunchKernelGGL((k_box3x3<false, false>), dim3(nb), dim3(BT_NT), 0, s, in, out, h, w, d, P, m, v, ac, gsave);
@@ -304,7 +314,7 @@ int cvx::adam_run_impl(const float* F2, const float* M2, int C, int h, int w, in
         const AdamConsts ac = {(float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)sqrt(bc2), (float)(-(1.0 / bc1)), adam_sqrt_table()};
         if (fast == 2 && fused) { if ((rc = launch_box3_fast(P, U, h, w, d, nullptr, nullptr, nullptr, 1.0, 1.0, nullptr, s))) return rc; }   // "fast_all": separable forward boxes too
         else if (fast == 2 && sm->kind == 0) { if ((rc = launch_boxchain_fast(P, U, h, w, d, *sm, false, s))) return rc; }             // ... for a box chain of the sweep
-        else if (fused) { if ((rc = launch_box3x3(P, U, h, w, d, false, nullptr, nullptr, nullptr, ac, nullptr, s))) return rc; }
+        else if (fused) { if ((rc = launch_box3x3(P, U, h, w, d, false, nullptr, nullptr, nullptr, ac, nullptr, false, s))) return rc; }
         else if ((rc = launch_smoother(P, U, t1, 3, h, w, d, *sm, false, s))) return rc;
         profile_mark_kernel("adam.forward_boxes", s);
         const bool last = it == niter - 1;
@@ -323,9 +333,11 @@ int cvx::adam_run_impl(const float* F2, const float* M2, int C, int h, int w, in
                 if (gsave) (void)hipMemcpyAsync(gsave, t2, sizeof(float) * 3 * V, hipMemcpyDeviceToDevice, s);
             }
         } else {
-        if ((rc = launch_warp_grad(Fcl, Mcl, C, h, w, d, U, base_h, base_w, base_d, gsc, cH, cW, cD, gU, f16_features, s))) return rc;
+        // one decision for both launches: gU / 27 from the warp kernel exactly when the adjoint runs on the tiles
+        const bool prediv = fused && options().box_prediv != 0 && box3_tile_choice(gU, nullptr, h, w, d, true, P, m, v, gsave) != 0;
+        if ((rc = launch_warp_grad(Fcl, Mcl, C, h, w, d, U, base_h, base_w, base_d, gsc, cH, cW, cD, gU, f16_features, prediv, s))) return rc;
         profile_mark_kernel("adam.warp_gradient", s);
-        if (fused) { if ((rc = launch_box3x3(gU, nullptr, h, w, d, true, P, m, v, ac, gsave, s))) return rc; }
+        if (fused) { if ((rc = launch_box3x3(gU, nullptr, h, w, d, true, P, m, v, ac, gsave, prediv, s))) return rc; }
         else {
             if ((rc = launch_smoother(gU, t2, t1, 3, h, w, d, *sm, true, s))) return rc;
             hipLaunchKernelGGL(k_adam_update, dim3((unsigned)cdiv64((int64_t)(3 * V), 256)), dim3(256), 0, s, t2, P, m, v, 3 * V, ac);

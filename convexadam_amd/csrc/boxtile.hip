@@ -100,6 +100,42 @@ __device__ __forceinline__ void bt_walk(int L, Load load, Prep prep, Emit emit) 
     }
 }
 
+// ---- readiness flags between the passes (option box_tile_sync = 1) -----------------------------------------------------------------
+// One LDS flag per (segment, row) of stages 1 and 2, set once by the item that wrote it.  A wavefront finishes all its items of pass k
+// before it waits for anything of pass k + 1, so every wait is on an item that never waits: no cycle, all wavefronts are resident.
+constexpr unsigned BT_SPIN_MAX = 1u << 20;          // polls of 64 clocks (~28 ms) before a wait gives up (never in correct code)
+__device__ unsigned bt_sync_errors;                 // expired waits since the last cvx_box_tile_sync_errors(1)
+
+__device__ __forceinline__ void bt_publish(int* flag, bool leader) {
+#ifdef CVX_RACE_JITTER
+    cvx_jitter();
+#endif
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");           // the item's stage stores before its flag
+    if (leader) __hip_atomic_store(flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+// Waits (wave-uniformly) until the items of the previous pass that wrote rows r .. r + 2, planes [a, b) of their stage are done; that
+// stage has `planes` planes cut into ns segments of rows of Y.  Lane q checks row r + q % 3 and segments q / 3, q / 3 + 5, ..
+__device__ __forceinline__ void bt_wait(const int* flags, int Y, int planes, int ns, FastDiv dn, int r, int a, int b, int q) {
+#ifdef CVX_RACE_JITTER
+    cvx_jitter();
+#endif
+    for (unsigned spin = 0;; ++spin) {
+        bool ok = true;
+        if (q < 15)
+            for (int sg = q / 3; sg < ns; sg += 5)
+                if (fastdiv(sg * planes, dn) < b && fastdiv((sg + 1) * planes, dn) > a)
+                    ok = ok && __hip_atomic_load(flags + sg * Y + r + q % 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != 0;
+        if (__builtin_amdgcn_ballot_w64(!ok) == 0) break;
+        if (spin >= BT_SPIN_MAX) {
+            if (q == 0) atomicAdd(&bt_sync_errors, 1u);
+            break;
+        }
+        __builtin_amdgcn_s_sleep(1);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
 }  // namespace
 
 // TZ x TY x (4 TXQ) output tile, NW wavefronts, NS1 / NS2 / NS3 z segments per row in passes 1 / 2 / 3 (run-time: they only cut the
@@ -107,16 +143,28 @@ __device__ __forceinline__ void bt_walk(int L, Load load, Prep prep, Emit emit) 
 // BACKWARD: ATen's avg_pool3d_backward order of the three adjoint boxes -- every tap is gradOut / 27 (IEEE division, the dividend may be
 // -0.0), the sums are plain: the global taps are divided when they are consumed, stages 1 and 2 are stored divided, the last pass keeps
 // the sum; ADAM: the last pass applies torch.optim.Adam's update to P, m, v in place (gsave optionally receives G) instead of storing G.
-template <int TZ, int TY, int TXQ, int NW, int WPS, bool BACKWARD, bool ADAM>
+// PREDIV: the adjoint's input taps arrive divided already (k_warp_grad<.., true> stores gU / 27 with the same expression), so pass 1
+// only shifts the halo columns -- each gU value is loaded ~3.5 times, and divided once instead.
+// SYNC: the passes hand over through the readiness flags above instead of two workgroup barriers, so a wavefront that runs out of items
+// of one pass starts the next pass's items whose input rows are complete (pass 1 has 80 items for 64 slots: 12 of 16 wavefronts would
+// otherwise idle through its second round).  Bit-identical, but measured slower than the barriers: option box_tile_sync.
+// census (option tile_census_ptr): per wavefront 8 words {start, pass 1 done, barrier 1 passed (SYNC: first pass-2 item's wait over),
+// pass 2 done, barrier 2 passed (SYNC: first pass-3 item's wait over), pass 3 done, 0, placement} in 100 MHz ticks, workgroups < 1024;
+// a wavefront without items in a pass leaves its SYNC stamp 0.
+template <int TZ, int TY, int TXQ, int NW, int WPS, bool BACKWARD, bool ADAM, bool PREDIV, bool SYNC>
 __global__ __launch_bounds__(64 * NW, WPS) void k_box3_tile(const float* __restrict__ in, float* __restrict__ out, int h, int w, int d,
                                                            int ntz, int nty, int ntx, int ntiles, int NS1, int NS2, int NS3, FastDiv dvz, FastDiv dvx, FastDiv dvy,
                                                            FastDiv dn1, FastDiv dn2, FastDiv dn3, float* __restrict__ P, float* __restrict__ m, float* __restrict__ v, AdamConsts ac,
-                                                           float* __restrict__ gsave) {
+                                                           float* __restrict__ gsave, unsigned long long* __restrict__ census) {
     constexpr int TX = 4 * TXQ, RS = TX + 4;                          // LDS row stride (floats): stage 1 holds TX + 4 columns
     constexpr int Z1 = TZ + 4, Y1 = TY + 4, Z2 = TZ + 2, Y2 = TY + 2;
     constexpr int SLOTS = NW * 4;                                      // 16-lane items per round
+    constexpr int NF1 = Z1 / 2 * Y1, NF2 = Z2 / 2 * Y2;                // flags: at most planes / 2 segments (launch_tile_t)
     static_assert(TXQ + 2 <= 16, "a row of quads must fit 16 lanes");
     __shared__ __attribute__((aligned(16))) float S[Z1 * Y1 * RS + Z2 * Y2 * RS + 8];
+    __shared__ int RF[SYNC ? NF1 + NF2 : 1];
+    int* F1 = RF;
+    int* F2 = RF + NF1;
     float* S1 = S;
     float* S2 = S + Z1 * Y1 * RS;
     const int per_xcd = (int)(gridDim.x >> 3);
@@ -133,6 +181,13 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_box3_tile(const float* __restr
     const __amdgpu_buffer_rsrc_t ir = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(ic), 0, (int)(V * sizeof(float)), 0x00020000);
     const int tid = threadIdx.x, q = tid & 15, slot = tid >> 4;
     const int wd = w * d;
+    if (SYNC) {
+        for (int i = tid; i < NF1 + NF2; i += 64 * NW) RF[i] = 0;
+        cvx_barrier();
+    }
+    unsigned long long* cw = (census && b < 1024) ? census + ((size_t)b * NW + __builtin_amdgcn_readfirstlane(tid >> 6)) * 8 : nullptr;
+    auto stamp = [&](int k) { if (cw && (tid & 63) == 0) cw[k] = __builtin_amdgcn_s_memrealtime(); };
+    stamp(0);
 
     // ---- pass 1: stage 0 (global) -> S1.  Lane q: columns x0 - 4 + 4q .. + 3 (local index i = 4q .. 4q + 3; kept: i = 2 .. TX + 5)
     for (int item = slot; item < Y1 * NS1; item += SLOTS) {
@@ -158,7 +213,7 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_box3_tile(const float* __restr
             }
         };
         auto prep = [&](BTWin& t) {
-            if (BACKWARD) {                       // taps of the adjoint: gradOut / 27, sign of zero kept
+            if (BACKWARD && !PREDIV) {            // taps of the adjoint: gradOut / 27, sign of zero kept
 #pragma unroll
                 for (int i = 0; i < 3; ++i)
 #pragma unroll
@@ -185,13 +240,19 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_box3_tile(const float* __restr
             if (q < TXQ + 1) lds_store2(p + 2, f32x2{o[2], o[3]});
         };
         bt_walk(L, load, prep, emit);
+        if (SYNC) bt_publish(F1 + sg * Y1 + r, q == 0);
     }
-    cvx_barrier();
+    stamp(1);
+    if (!SYNC) { cvx_barrier(); stamp(2); }
 
     // ---- pass 2: S1 -> S2.  Lane q < TXQ + 1: stage-2 index j2 = 4q .. 4q + 3  <->  x = x0 - 1 + j2; window = S1 index 4q .. 4q + 5
     for (int item = slot; item < Y2 * NS2; item += SLOTS) {
         const int r = item % Y2, sg = item / Y2;
         const int p0 = fastdiv(sg * Z2, dn2), L = fastdiv((sg + 1) * Z2, dn2) - p0;   // stage-2 planes p0 ..  <->  z = z0 - 1 + p
+        if (SYNC) {                                                    // S1 rows r .. r + 2, planes p0 .. p0 + L + 1
+            bt_wait(F1, Y1, Z1, NS1, dn1, r, p0, p0 + L + 2, q);
+            if (item == slot) stamp(2);
+        }
         if (q < TXQ + 1) {
             const float* src = S1 + (p0 * Y1 + r) * RS + 4 * q;
             auto load = [&](int n, BTWin& t) {
@@ -221,13 +282,19 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_box3_tile(const float* __restr
             };
             bt_walk(L, load, [](BTWin&) {}, emit);
         }
+        if (SYNC) bt_publish(F2 + sg * Y2 + r, q == 0);
     }
-    cvx_barrier();
+    stamp(3);
+    if (!SYNC) { cvx_barrier(); stamp(4); }
 
     // ---- pass 3: S2 -> U.  Lane q < TXQ: columns x0 + 4q .. + 3; window = S2 index 4q .. 4q + 5
     for (int item = slot; item < TY * NS3; item += SLOTS) {
         const int r = item % TY, sg = item / TY;
         const int p0 = fastdiv(sg * TZ, dn3), L = fastdiv((sg + 1) * TZ, dn3) - p0;
+        if (SYNC) {                                                    // S2 rows r .. r + 2, planes p0 .. p0 + L + 1
+            bt_wait(F2, Y2, Z2, NS2, dn2, r, p0, p0 + L + 2, q);
+            if (item == slot) stamp(4);
+        }
         const int gy = y0 + r, gx = x0 + 4 * q;
         if (q < TXQ && gy < w && gx < d) {
             const float* src = S2 + (p0 * Y2 + r) * RS + 4 * q;
@@ -263,6 +330,11 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_box3_tile(const float* __restr
             bt_walk(L, load, [](BTWin&) {}, emit);
         }
     }
+    stamp(5);
+    if (cw && (tid & 63) == 0) {
+        cw[6] = 0;
+        cw[7] = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11)) | ((unsigned long long)__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11)) << 32);
+    }
 }
 
 // rows of whole 16-byte quads, 16-byte aligned volumes; 3 channels
@@ -274,17 +346,24 @@ bool box3_tile_fwd_supported(const float* in, const float* out, int h, int w, in
 
 template <int TZ, int TY, int TXQ, int NW, int WPS>
 static int launch_tile_t(const float* in, float* out, int h, int w, int d, int ns1, int ns2, int ns3, bool backward, float* P, float* m, float* v,
-                         AdamConsts ac, float* gsave, hipStream_t s) {
+                         AdamConsts ac, float* gsave, bool prediv, hipStream_t s) {
     const int ntz = cdiv(h, TZ), nty = cdiv(w, TY), ntx = cdiv(d, 4 * TXQ);
     const int ntiles = 3 * ntz * nty * ntx;
     const unsigned nb = (unsigned)((ntiles + 7) / 8 * 8);
     // segments of at least two planes (bt_walk), at most one per two planes
     auto clampns = [](int ns, int planes) { return ns < 1 ? 1 : (ns > planes / 2 ? planes / 2 : ns); };
     const int a1 = clampns(ns1, TZ + 4), a2 = clampns(ns2, TZ + 2), a3 = clampns(ns3, TZ);
-#define CVX_BT_LAUNCH(B, A) hipLaunchKernelGGL((k_box3_tile<TZ, TY, TXQ, NW, WPS, B, A>), dim3(nb), dim3(64 * NW), 0, s, in, out, h, w, d, ntz, nty, ntx, ntiles, a1, a2, a3, fastdiv_make(ntz), fastdiv_make(ntx), fastdiv_make(nty), fastdiv_make(a1), fastdiv_make(a2), fastdiv_make(a3), P, m, v, ac, gsave)
-    if (!backward) CVX_BT_LAUNCH(false, false);
-    else if (!P) CVX_BT_LAUNCH(true, false);
-    else CVX_BT_LAUNCH(true, true);
+    const bool sync = options().box_tile_sync != 0;
+    // debugging aid (option tile_census_ptr, tools/boxtile_census.py): forward tiles from word 0, adjoint tiles from word 8 * 16 * 1024
+    unsigned long long* census = reinterpret_cast<unsigned long long*>(options().tile_census_ptr);
+    if (census && backward) census += 8 * 16 * 1024;
+#define CVX_BT_LAUNCH(B, A, D, Y) hipLaunchKernelGGL((k_box3_tile<TZ, TY, TXQ, NW, WPS, B, A, D, Y>), dim3(nb), dim3(64 * NW), 0, s, in, out, h, w, d, ntz, nty, ntx, ntiles, a1, a2, a3, fastdiv_make(ntz), fastdiv_make(ntx), fastdiv_make(nty), fastdiv_make(a1), fastdiv_make(a2), fastdiv_make(a3), P, m, v, ac, gsave, census)
+#define CVX_BT_SYNC(B, A, D) do { if (sync) CVX_BT_LAUNCH(B, A, D, true); else CVX_BT_LAUNCH(B, A, D, false); } while (0)
+    if (!backward) CVX_BT_SYNC(false, false, false);
+    else if (!P) { if (prediv) CVX_BT_SYNC(true, false, true); else CVX_BT_SYNC(true, false, false); }
+    else if (prediv) CVX_BT_SYNC(true, true, true);
+    else CVX_BT_SYNC(true, true, false);
+#undef CVX_BT_SYNC
 #undef CVX_BT_LAUNCH
     return check_last("box3_tile");
 }
@@ -295,19 +374,21 @@ static int launch_tile_t(const float* in, float* out, int h, int w, int d, int n
 // kind 2 with 4 / 3 / 4 segments 15.6-16.6 us, kind 1 18.7-19.6 us; both kinds issue the marching kernel's 8.1 M VALU wave-instructions
 // (the 27 additions per output and stage are ATen's) and run at the ~3.3 clocks per instruction of four wavefronts per SIMD -- the LDS
 // footprint of the stage tiles leaves no room for more (a 64-register, 8-wavefront build of kind 1 spills and takes 25 us).
+// prediv (adjoint only): the input taps are gU / 27 already (launch_warp_grad(.., prediv = true)).
 int launch_box3_tile(const float* in, float* out, int h, int w, int d, int variant, bool backward, float* P, float* m, float* v, AdamConsts ac,
-                     float* gsave, hipStream_t s) {
+                     float* gsave, bool prediv, hipStream_t s) {
     const int kind = variant / 1000, ns = variant % 1000;
     int ns1 = ns / 100, ns2 = (ns / 10) % 10, ns3 = ns % 10;
+    prediv = prediv && backward;
     if (kind == 1) {
         if (!ns) { ns1 = 5; ns2 = 3; ns3 = 4; }
-        return launch_tile_t<12, 8, 14, 8, 4>(in, out, h, w, d, ns1, ns2, ns3, backward, P, m, v, ac, gsave, s);
+        return launch_tile_t<12, 8, 14, 8, 4>(in, out, h, w, d, ns1, ns2, ns3, backward, P, m, v, ac, gsave, prediv, s);
     }
     if (!ns) { ns1 = 4; ns2 = 3; ns3 = 4; }
-    return launch_tile_t<12, 16, 14, 16, 4>(in, out, h, w, d, ns1, ns2, ns3, backward, P, m, v, ac, gsave, s);
+    return launch_tile_t<12, 16, 14, 16, 4>(in, out, h, w, d, ns1, ns2, ns3, backward, P, m, v, ac, gsave, prediv, s);
 }
 int launch_box3_tile_fwd(const float* in, float* out, int h, int w, int d, int variant, hipStream_t s) {
-    return launch_box3_tile(in, out, h, w, d, variant, false, nullptr, nullptr, nullptr, AdamConsts{}, nullptr, s);
+    return launch_box3_tile(in, out, h, w, d, variant, false, nullptr, nullptr, nullptr, AdamConsts{}, nullptr, false, s);
 }
 
 // automatic choice (option box_fwd_tile / box_bwd_tile = -1): the large tiles when they fill the chip
@@ -317,3 +398,14 @@ int box3_tile_fwd_auto(int h, int w, int d) {
 }
 
 }  // namespace cvx
+
+// expired flag waits of k_box3_tile (option box_tile_sync = 1) on the current device since the last reset; synchronises the device
+extern "C" int cvx_box_tile_sync_errors(int reset) {
+    unsigned n = 0;
+    if (hipDeviceSynchronize() != hipSuccess || hipMemcpyFromSymbol(&n, HIP_SYMBOL(cvx::bt_sync_errors), sizeof(n)) != hipSuccess) return CVX_ERR_LAUNCH;
+    if (reset && n) {
+        const unsigned z = 0;
+        if (hipMemcpyToSymbol(HIP_SYMBOL(cvx::bt_sync_errors), &z, sizeof(z)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return CVX_ERR_LAUNCH;
+    }
+    return (int)n;
+}

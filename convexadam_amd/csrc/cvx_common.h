@@ -128,6 +128,12 @@ struct Options {
                                    //    passes' 0.08 ms per pair takes back
     long long fbox_tile;           // adam_mode "fast": tile shape of the separable adjoint-box + Adam kernel (adamfast.hip): 0 = automatic, 1 = 8x10x24,
                                    //    2 = 8x10x56, 3 = 16x10x24, 4 = 16x10x56, 5 = 8x8x32, 6 = 4x10x24 (bit-identical)
+    long long box_tile_sync;       // three-box tiles (boxtile.hip): 1 = the passes hand over through per-row readiness flags in LDS, 0 (default) = two workgroup barriers
+                                   //    (bit-identical; MEASURED SLOWER on the benchmark grid: forward tiles 16.85 vs 15.94 us)
+    long long box_prediv;          // exact Adam loop with the adjoint boxes on tiles: 1 (default) = k_warp_grad stores gU / 27 and the tiles do not divide their input taps,
+                                   //    0 = the tiles divide every tap they load (bit-identical)
+    long long tile_census_ptr;     // debugging aid: device address of a uint64 buffer of 2 x 8 x 16 x 1024 words; k_box3_tile records per wavefront the clocks of its passes
+                                   //    (boxtile.hip, tools/boxtile_census.py; 0 = off)
 };
 // All three read the context bound to the calling thread (cvx_context_bind / cvx_pair_params.ctx), else the process default context;
 // launchers copy what they need into kernel arguments at enqueue time (api.hip).
@@ -457,13 +463,14 @@ int launch_box3_tile_fwd(const float* in, float* out, int h, int w, int d, int v
 int box3_tile_fwd_auto(int h, int w, int d);       // variant for this grid, 0 = keep the marching kernel
 // the same tiles for the exact adjoint boxes (ATen's avg_pool3d_backward order), optionally with the Adam update in the last pass
 bool box3_tile_supported(const float* in, const float* out, int h, int w, int d, const float* P, const float* m, const float* v, const float* gsave);
+// (prediv: the adjoint's input is gU / 27 already, launch_warp_grad(.., prediv = true))
 int launch_box3_tile(const float* in, float* out, int h, int w, int d, int variant, bool backward, float* P, float* m, float* v, AdamConsts ac,
-                     float* gsave, hipStream_t s);
+                     float* gsave, bool prediv, hipStream_t s);
 // warp.hip: [C][V] -> [CP/4][V][4] feature copies and the warp + data-term gradient of one Adam iteration
 // (half: records of four half-precision values -- fp16 storage of the pooled features -- instead of four floats)
 int launch_to_chunked(const float* in, int C, size_t V, float* out, bool half, hipStream_t s);
 int launch_warp_grad(const float* Fcl, const float* Mcl, int C, int h, int w, int d, const float* U, const float* bh,
-                     const float* bw, const float* bd, float gsc, float cH, float cW, float cD, float* gU, bool half, hipStream_t s);
+                     const float* bw, const float* bd, float gsc, float cH, float cW, float cD, float* gU, bool half, bool prediv, hipStream_t s);
 // adamfast.hip: adam_mode "fast" -- FMA / factored warp + gradient (float32 records) and the separable adjoint boxes with the Adam
 // update in the epilogue (P != nullptr: in-place update of P, m, v with G = box(in); P == nullptr: out = box(in)); bc1, bc2 = the bias
 // corrections 1 - beta^step of this iteration

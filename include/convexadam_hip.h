@@ -79,6 +79,9 @@ int cvx_device_count(void);            /* number of visible HIP devices (0 on a 
  *                       (cvx_corr_opts.fast = 2; same winners and field bits as the exact volumes; below 16 channels); 1 = the role kernel of
  *                       corrfused.hip, 2 = the staged kernel of corrcert.hip (every supported channel count); 0 = exact volumes
  *   ic_fused            1: inverse consistency in one launch (measured slower, off by default; bit-identical)
+ *   box_tile_sync       three-box tiles of the Adam loop: 1 = the passes hand over through per-row readiness flags (measured slower), 0 (default) = workgroup barriers
+ *   box_prediv          exact Adam loop: 1 (default) = the warp kernel stores gU / 27 for the adjoint box tiles, 0 = the tiles divide their taps
+ *   tile_census_ptr     debugging aid: device buffer of 2 x 8 x 16 x 1024 uint64 for per-wavefront pass clocks of the box tiles (0 = off)
  * Workspace sizes (cvx_*_workspace_bytes) depend on some switches: query them with the same context / options the call will use.
  *
  * State model.  Switches and the two reference-build tables below live in a CONTEXT.  Every entry point uses the context bound to the
@@ -102,6 +105,10 @@ int cvx_context_set_option(cvx_context* ctx, const char* name, long long value);
 long long cvx_context_get_option(const cvx_context* ctx, const char* name);
 int cvx_set_option(const char* name, long long value);
 long long cvx_get_option(const char* name);
+/* Waits of the box tiles' readiness flags (box_tile_sync = 1) that gave up after their spin bound on the current device since the last reset
+ * (never in correct code: the kernel then continues, its results are not trustworthy).  Synchronises the device; reset != 0 clears the count.
+ * Returns the count, or CVX_ERR_LAUNCH. */
+int cvx_box_tile_sync_errors(int reset);
 
 /* host helpers (exact restatements of torch.linspace / affine_grid tables) ----------------------- */
 /* F.affine_grid(eye, size S, align_corners=False) identity coordinate along an axis of extent S.
