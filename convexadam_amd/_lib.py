@@ -145,6 +145,9 @@ SIGNATURES = {
     "cvx_tps_eval_f32": (_i, [_vp, _i64, _vp, _vp, _i, _i, _vp, _vp]),
     "cvx_tps_dense_f32": (_i, [_i, _i, _i, _vp, _vp, _i, _i, _vp, _vp]),
     "cvx_resize_trilinear_ac_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _i, _vp]),
+    "cvx_rigid_lts_workspace_bytes": (_sz, [_i64]),
+    "cvx_rigid_lts_f32": (_i, [_vp, _i, _vp, _i, _i64, _i, _vp, _vp, _vp, _sz, _vp]),
+    "cvx_affine_warp_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
 }
 
 _lib = None

@@ -30,6 +30,7 @@ from .convex_adam_utils import coupled_convex, correlate, gpu_usage, inverse_con
 from .convex_adam_utils import MINDSSC as _MINDSSC
 from .convex_adam_MIND import extract_features as _extract_features
 from .convex_adam_nnUNet import extract_features as _extract_features_nnunet
+from .rigid import find_rigid_3d, least_trimmed_rigid  # noqa: F401  (self_configuring/convexAdam_hyper_util.py:326-346)
 
 
 def MINDSSC(img, radius=2, dilation=2):

@@ -456,3 +456,5 @@ def gpu_usage():
 
 # thin-plate-spline densification (l2r_2021_convexAdam_task1_docker.py:198-262,365-387): csrc/tps.hip
 from .tps import TPS, thin_plate_dense, tps_densify  # noqa: E402,F401
+# least-trimmed rigid fit and fused affine warp (convex_adam_utils.py:173-193, l2r_2020_convexAdam_CuRIOUS.py:349-390): csrc/rigid.hip
+from .rigid import affine_warp, find_rigid_3d, least_trimmed_rigid, rigid_from_field  # noqa: E402,F401

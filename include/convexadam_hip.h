@@ -530,6 +530,24 @@ int cvx_tps_dense_f32(int s0, int s1, int s2, const float* centres, const float*
  *   in [C][h][w][d] -> out [C][H][W][D]; bit-identical to ATen's CPU kernel in float32 */
 int cvx_resize_trilinear_ac_f32(const float* in, int C, int h, int w, int d, float* out, int H, int W, int D, void* stream);
 
+/* least-trimmed rigid fit and fused affine warp (csrc/rigid.hip) ------------------------------------------------------------------
+ * replaces find_rigid_3d / least_trimmed_rigid (convex_adam_utils.py:173-193) and the affine_grid + grid_sample warp of
+ *   l2r_2020_convexAdam_CuRIOUS.py:367-390.
+ * cvx_rigid_lts_f32    : iters == 1: find_rigid_3d(fixed, moving) on columns 0..2 (ld >= 3); iters >= 2: least_trimmed_rigid(fixed, moving,
+ *                        iter=iters) on (n, 4) points (ld == 4): fit 0 on all n points, fit k on the n/2 points with the smallest residuals
+ *                        ||moving_i - fixed_i T^T|| (all four columns) under fit k-1, ties at the threshold to the lowest index.  T [4][4]
+ *                        (device) = [R t; 0 0 0 1] of the last fit, R the optimal proper rotation; inliers (device [n], may be NULL) = 1 for
+ *                        the points of the last fit.  2 <= n <= 2^28.  One workgroup; SYNCHRONISES `stream` (it reads the fit status back):
+ *                        a non-finite coordinate among the points of a fit returns CVX_ERR_INVALID_ARG and leaves T and inliers unwritten */
+size_t cvx_rigid_lts_workspace_bytes(int64_t n);
+int cvx_rigid_lts_f32(const float* fixed, int ld_fixed, const float* moving, int ld_moving, int64_t n, int iters, float* T,
+                      unsigned char* inliers, void* workspace, size_t workspace_bytes, void* stream);
+/* cvx_affine_warp_f32  : F.grid_sample(vol, F.affine_grid(theta, (1,C,ho,wo,do), align_corners=False), mode, 'zeros', align_corners=False)
+ *                        without the grid: vol [C][h][w][d], theta [3][4] row-major in DEVICE memory, mode 0 bilinear / 1 nearest
+ *                        -> out [C][ho][wo][do]; bit-identical to ATen's CPU affine_grid + grid_sample in float32 */
+int cvx_affine_warp_f32(const float* vol, int C, int h, int w, int d, const float* theta, int ho, int wo, int dd, int mode, float* out,
+                        void* stream);
+
 #pragma GCC visibility pop
 
 #ifdef __cplusplus
