@@ -232,9 +232,10 @@ __device__ __forceinline__ void lds_store2(float* p, f32x2 v) { *(volatile lds_f
 
 // Exact x / D for the divisors of the box filters and poolings (D in {8, 27, 64, 125, 343}):
 //   q = x*r ; e = fma(-D, q, x) ; q' = fma(e, r, q)      with r = RN(1/D)
-// equals the correctly rounded IEEE quotient for EVERY float x (verified exhaustively over all 2^32 bit
-// patterns, scratch/div27.c in the build log) except that -0.0 maps to +0.0, which no caller can produce:
+// equals the correctly rounded IEEE quotient for every FINITE float x (verified exhaustively over the finite bit
+// patterns, tools/verify_div_exact.c) except that -0.0 maps to +0.0, which no caller can produce:
 // the dividends are sums that start from +0.0.  3 instructions instead of the ~15 of the IEEE sequence.
+// +-inf gives NaN (e = fma(-D, inf, inf)): where a dividend can be infinite, use div_exact_inf.
 template <int D>
 __device__ __forceinline__ float div_exact(float x) {
     static_assert(D == 8 || D == 27 || D == 64 || D == 125 || D == 343, "divisor not verified");
@@ -243,6 +244,9 @@ __device__ __forceinline__ float div_exact(float x) {
     const float e = __builtin_fmaf(-(float)D, q, x);
     return __builtin_fmaf(e, r, q);
 }
+// the same for dividends that may be +-inf (IEEE: +-inf / D = +-inf); NaN stays NaN either way
+template <int D>
+__device__ __forceinline__ float div_exact_inf(float x) { return __builtin_isinf(x) ? x : div_exact<D>(x); }
 
 // ATen outer-dimension sum order over `n` values held in registers (see oracle outer_sum_rows):
 // plain sequential cascade (level step 16) or, for the last (ncols mod 32) columns, the 4-way

@@ -187,7 +187,7 @@ __global__ __launch_bounds__(256) void k_box_walk(const float* __restrict__ in, 
             float* op = oc + ((size_t)o * W + y) * D + x0;
             float v[CPT];
 #pragma unroll
-            for (int j = 0; j < CPT; ++j) v[j] = (K == 3 || K == 5 || K == 7) ? div_exact<(K == 3 || K == 5 || K == 7) ? K * K * K : 27>(sum[0][j]) : fdiv(sum[0][j], DIVF);
+            for (int j = 0; j < CPT; ++j) v[j] = (K == 3 || K == 5 || K == 7) ? div_exact_inf<(K == 3 || K == 5 || K == 7) ? K * K * K : 27>(sum[0][j]) : fdiv(sum[0][j], DIVF);
             if (CPT == 4) *reinterpret_cast<float4*>(op) = make_float4(v[0], v[1], v[CPT - 2], v[CPT - 1]);
             else *reinterpret_cast<float2*>(op) = make_float2(v[0], v[1]);
         }
