@@ -189,10 +189,17 @@ static int launch_box3x3(const float* in, float* out, int h, int w, int d, bool 
 
 using namespace cvx;
 
-extern "C" size_t cvx_adam_workspace_bytes(int C, int h, int w, int d) {
-    const size_t V = (size_t)h * w * d, CP = (size_t)(C + 3) / 4 * 4;
-    return 3 * (256 + sizeof(float) * 3 * V) + 2 * (256 + sizeof(float) * CP * (V + 1)) + 256;
+size_t cvx::adam_record_floats(int C, size_t V) { return (size_t)((C + 3) / 4 * 4) * (V + 1); }
+// gradient, two smoothing temporaries, the two feature records [CP/4][V + 1][4]
+struct AdamWs { float *gU, *t1, *t2, *Fcl, *Mcl; };
+static AdamWs adam_layout(Carver& cv, int C, size_t V) {
+    AdamWs a;
+    a.gU = cv.take<float>(3 * V); a.t1 = cv.take<float>(3 * V); a.t2 = cv.take<float>(3 * V);
+    a.Fcl = cv.take<float>(adam_record_floats(C, V)); a.Mcl = cv.take<float>(adam_record_floats(C, V));
+    return a;
 }
+
+extern "C" size_t cvx_adam_workspace_bytes(int C, int h, int w, int d) { Carver m; adam_layout(m, C, (size_t)h * w * d); return ws_query(m); }
 
 extern "C" int cvx_adam_run_f32(const float* F2, const float* M2, int C, int h, int w, int d, float* P, float* m, float* v,
                                 float lambda_weight, int niter, int step0, float cost_scale, const float* base_h,
@@ -276,10 +283,8 @@ int cvx::adam_run_impl(const float* F2, const float* M2, int C, int h, int w, in
         return fail(CVX_ERR_WORKSPACE, "cvx_adam_run_f32: workspace too small");
     hipStream_t s = as_stream(stream);
     const size_t V = (size_t)h * w * d;
-    Carver cv(workspace, workspace_bytes);
-    float* gU = cv.take<float>(3 * V);
-    float* t1 = cv.take<float>(3 * V);
-    float* t2 = cv.take<float>(3 * V);
+    Carver cv(workspace);
+    auto [gU, t1, t2, Fcl, Mcl] = adam_layout(cv, C, V);
     // generic smoother path unless it is the packaged chain of three 3^3 boxes (fused LDS kernels)
     const bool fused = !sm || (sm->kind == 0 && sm->n_boxes == 3 && sm->box_k[0] == 3 && sm->box_k[1] == 3 && sm->box_k[2] == 3);
     if (sm) {
@@ -291,9 +296,6 @@ int cvx::adam_run_impl(const float* F2, const float* M2, int C, int h, int w, in
     }
     if (fast && !fused && sm->kind == 0 && !boxchain_fast_supported(*sm, h, w, d))
         return fail(CVX_ERR_UNSUPPORTED, "adam_mode fast: box chain outside the separable kernel's range (odd sizes <= 9, lines of at most 320 voxels)");
-    const int CP = (C + 3) / 4 * 4;
-    float* Fcl = cv.take<float>((size_t)CP * (V + 1));
-    float* Mcl = cv.take<float>((size_t)CP * (V + 1));
     if (features_are_records) { Fcl = const_cast<float*>(F2); Mcl = const_cast<float*>(M2); }       // built by the producer (mind.hip::k_mind_finish_pool)
     else if (niter > 0) {
         int rc;

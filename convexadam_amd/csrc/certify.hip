@@ -603,31 +603,10 @@ void launch_corr_tail_compact(const float* fix, const float* mov, int C, int h, 
 // the coupled passes add the two ping-pong winner arrays and the work records
 // capacity of the plain pass's work list: four candidates per voxel on average, at least 64 K (a column holds n^3 entries)
 static size_t cert_work_cap(size_t v) { return 4 * v + 65536; }
-size_t corr_certify_workspace_bytes(int C, int h, int w, int d, int hw, bool plain) {
-    (void)C;
-    const size_t v = (size_t)h * w * d;
-    const int n = 2 * hw + 1;
-    size_t used = 0;
-    used = carve_size(used, sizeof(unsigned long long) * v);      // key
-    used = carve_size(used, sizeof(unsigned) * v);                // sec
-    used = carve_size(used, sizeof(int) * v);                     // idx0
-    used = carve_size(used, sizeof(float) * v);                   // smin
-    used = carve_size(used, sizeof(unsigned) * v);                // list
-    used = carve_size(used, sizeof(int) * 16);                    // counts
-    used = carve_size(used, sizeof(unsigned long long) * cert_work_cap(v));   // work list of the plain pass
-    used = carve_size(used, sizeof(float) * 32 * n);              // tail
-    if (!plain) {
-        for (int i = 0; i < 2; ++i) used = carve_size(used, sizeof(int) * v);   // idxA, idxB
-        used = carve_size(used, sizeof(CertRec) * v);             // records
-    }
-    return used + 256;
-}
-
 struct CertCarve { unsigned long long* key; unsigned* sec; int* idx0; int* idxA; int* idxB; float* smin; unsigned* list; CertRec* rec; int* counts; float* tail; unsigned long long* work; unsigned work_cap; };
-static CertCarve cert_carve(void* workspace, size_t workspace_bytes, int h, int w, int d, int hw, bool plain = false) {
+static CertCarve cert_layout(Carver& cv, int h, int w, int d, int hw, bool plain) {
     const size_t v = (size_t)h * w * d;
     const int n = 2 * hw + 1;
-    Carver cv(workspace, workspace_bytes);
     CertCarve c{};
     c.key = cv.take<unsigned long long>(v);
     c.sec = cv.take<unsigned>(v);
@@ -636,7 +615,7 @@ static CertCarve cert_carve(void* workspace, size_t workspace_bytes, int h, int 
     c.list = cv.take<unsigned>(v);
     c.counts = cv.take<int>(16);
     c.work_cap = (unsigned)cert_work_cap(v);
-    c.work = cv.take<unsigned long long>(c.work_cap);
+    c.work = cv.take<unsigned long long>(c.work_cap);       // work list of the plain pass
     c.tail = cv.take<float>((size_t)32 * n);
     if (!plain) {
         c.idxA = cv.take<int>(v); c.idxB = cv.take<int>(v);
@@ -644,6 +623,7 @@ static CertCarve cert_carve(void* workspace, size_t workspace_bytes, int h, int 
     }
     return c;
 }
+size_t corr_certify_workspace_bytes(int, int h, int w, int d, int hw, bool plain) { Carver m; cert_layout(m, h, w, d, hw, plain); return ws_query(m); }
 static CertGeo cert_geo(int C, int h, int w, int d, int hw) {
     CertGeo g;
     g.C = C; g.h = h; g.w = w; g.d = d; g.hw = hw; g.n = 2 * hw + 1; g.K = g.n * g.n * g.n;
@@ -698,7 +678,8 @@ static int cert_plain(CertArgs& A, int nprob, bool arm, hipStream_t s) {
 int corr_certified_argmin(const float* ssdu, const float* fix, const float* mov, int C, int h, int w, int d, int hw, int64_t* argmin,
                           void* workspace, size_t workspace_bytes, hipStream_t s) {
     if (workspace_bytes < corr_certify_workspace_bytes(C, h, w, d, hw, true)) return fail(CVX_ERR_WORKSPACE, "certified argmin: workspace too small");
-    const CertCarve c = cert_carve(workspace, workspace_bytes, h, w, d, hw, true);
+    Carver cv(workspace);
+    const CertCarve c = cert_layout(cv, h, w, d, hw, true);
     CertArgs A{};
     A.g = cert_geo(C, h, w, d, hw);
     A.p[0] = cert_prob(ssdu, fix, mov, c, nullptr, argmin);
@@ -717,10 +698,11 @@ int coupled_convex_cert_impl(const float* ssduA, const float* fixA, const float*
     CertArgs A{};
     A.g = cert_geo(C, h, w, d, hw);
     A.mesh = mesh;
-    const CertCarve ca = cert_carve(wsA, workspace_bytes, h, w, d, hw);
+    Carver cva(wsA), cvb(wsB);
+    const CertCarve ca = cert_layout(cva, h, w, d, hw, false);
     A.p[0] = cert_prob(ssduA, fixA, movA, ca, outA, nullptr);
     A.p[1] = A.p[0];
-    if (ssduB) { const CertCarve cb = cert_carve(wsB, workspace_bytes, h, w, d, hw); A.p[1] = cert_prob(ssduB, fixB, movB, cb, outB, nullptr); }
+    if (ssduB) { const CertCarve cb = cert_layout(cvb, h, w, d, hw, false); A.p[1] = cert_prob(ssduB, fixB, movB, cb, outB, nullptr); }
     if (stage == 1) { cert_arm(A, nprob, s); return check_last("certified argmin"); }
     if (stage == 2) { cert_stream(A, 0, 1, s); return check_last("certified argmin"); }
     if (stage == 3) { if (nprob > 1) cert_stream(A, 1, 1, s); return check_last("certified argmin"); }

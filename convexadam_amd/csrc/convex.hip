@@ -514,15 +514,17 @@ int launch_argmin_keys(const void* ssd, bool f16, int K, size_t v, unsigned long
     if (f16) return argmin_pass(static_cast<const __half*>(ssd), nullptr, nullptr, 0.0f, false, K, v, keys, arm, s);
     return argmin_pass(static_cast<const float*>(ssd), nullptr, nullptr, 0.0f, false, K, v, keys, arm, s);
 }
-int* coupled_ws_counts(void* workspace, size_t workspace_bytes, int h, int w, int d, int disp_hw) {
+CoupledWs coupled_layout(Carver& cv, int h, int w, int d, int disp_hw) {
     const int n = 2 * disp_hw + 1, K = n * n * n;
     const size_t v = (size_t)h * w * d;
-    Carver cv(workspace, workspace_bytes);
-    for (int i = 0; i < 3; ++i) (void)cv.take<unsigned long long>(v);
-    (void)cv.take<int>(v);
-    (void)cv.take<float>(v);
-    const size_t list_cap = (size_t)((K + 255) / 256) * v;
-    return reinterpret_cast<int*>(cv.take<unsigned long long>(list_cap + 8) + list_cap);
+    CoupledWs c;
+    for (int i = 0; i < 3; ++i) c.keys[i] = cv.take<unsigned long long>(v);
+    c.idx = cv.take<int>(v);
+    c.smin = cv.take<float>(v);
+    const size_t list_cap = (size_t)((K + 255) / 256) * v;         // work items of the pruned passes, then the two list lengths
+    c.list = cv.take<unsigned long long>(list_cap + 8);
+    c.counts = c.list ? reinterpret_cast<int*>(c.list + list_cap) : nullptr;
+    return c;
 }
 
 int launch_argmin(const void* ssd, bool f16, const float* mesh, const float* u, float coef, bool coupled, int K, size_t v,
@@ -677,16 +679,7 @@ __global__ __launch_bounds__(1024) void k_ic_fallback(const float* f1, const flo
 
 using namespace cvx;
 
-extern "C" size_t cvx_coupled_convex_workspace_bytes(int h, int w, int d, int disp_hw) {
-    const int n = 2 * disp_hw + 1;
-    const size_t v = (size_t)h * w * d;
-    size_t used = 0;
-    for (int i = 0; i < 3; ++i) used = carve_size(used, sizeof(unsigned long long) * v);
-    used = carve_size(used, sizeof(int) * v);
-    used = carve_size(used, sizeof(float) * v);       // smin
-    used = carve_size(used, sizeof(unsigned long long) * ((size_t)((n * n * n + 255) / 256) * v + 8));   // work items of the pruned passes + count
-    return used + 256;
-}
+extern "C" size_t cvx_coupled_convex_workspace_bytes(int h, int w, int d, int disp_hw) { Carver m; coupled_layout(m, h, w, d, disp_hw); return ws_query(m); }
 
 
 extern "C" int cvx_coupled_convex_f32(const float* ssd, const int64_t* argmin, const float* mesh, int h, int w, int d,
@@ -717,15 +710,9 @@ static int coupled_core(const ST* ssd, const int64_t* argmin, const float* mesh,
     hipStream_t s = as_stream(stream);
     const int n = 2 * disp_hw + 1, K = n * n * n;
     const size_t v = (size_t)h * w * d;
-    Carver cv(workspace, workspace_bytes);
+    Carver cv(workspace);
     // three key buffers in rotation: pass p mins into keys[p % 3]; the gather that consumes pass p re-arms keys[(p+2) % 3]
-    unsigned long long* keys[3];
-    for (int i = 0; i < 3; ++i) keys[i] = cv.take<unsigned long long>(v);
-    int* idx = cv.take<int>(v);
-    float* smin = cv.take<float>(v);
-    const size_t list_cap = (size_t)((K + 255) / 256) * v;
-    unsigned long long* list = cv.take<unsigned long long>(list_cap + 8);
-    int* list_count = reinterpret_cast<int*>(list + list_cap);
+    const auto [keys, idx, smin, list, list_count] = coupled_layout(cv, h, w, d, disp_hw);
     const dim3 gv((unsigned)cdiv64((int64_t)v, 256), nprob);
     const bool no_prune_env = options().no_prune != 0;
     if (from_keys && (no_prune_env || !argmin_is_exact)) return fail(CVX_ERR_INVALID_ARG, "coupled_convex: key input needs the pruned path");
@@ -807,9 +794,15 @@ int cvx::coupled_convex_dual_impl(const void* ssdA, const int64_t* argminA, floa
     return coupled_dual_t(static_cast<const float*>(ssdA), argminA, outA, wsA, static_cast<const float*>(ssdB), argminB, outB, wsB, mesh, h, w, d, disp_hw, workspace_bytes, stream, counts_zeroed);
 }
 
-extern "C" size_t cvx_inverse_consistency_workspace_bytes(int h, int w, int d) {
-    return 2 * (256 + sizeof(float) * 3 * (size_t)h * w * d) + 256 + 256;      // two ping-pong fields + the synchronisation words of k_ic_persistent
+// two ping-pong fields + the synchronisation words of k_ic_persistent
+struct ICWs { float *t1, *t2; ICSync* sync; };
+static ICWs ic_layout(Carver& cv, size_t v) {
+    ICWs c;
+    c.t1 = cv.take<float>(3 * v); c.t2 = cv.take<float>(3 * v);
+    c.sync = cv.take<ICSync>(1);
+    return c;
 }
+extern "C" size_t cvx_inverse_consistency_workspace_bytes(int h, int w, int d) { Carver m; ic_layout(m, (size_t)h * w * d); return ws_query(m); }
 
 extern "C" int cvx_inverse_consistency_f32(const float* f1, const float* f2, int h, int w, int d, int iters,
                                            const float* base_h, const float* base_w, const float* base_d, float* o1,
@@ -821,16 +814,14 @@ extern "C" int cvx_inverse_consistency_f32(const float* f1, const float* f2, int
         return fail(CVX_ERR_WORKSPACE, "cvx_inverse_consistency_f32: workspace too small");
     hipStream_t s = as_stream(stream);
     const size_t v = (size_t)h * w * d, bytes = sizeof(float) * 3 * v;
-    Carver cv(workspace, workspace_bytes);
-    float* t1 = cv.take<float>(3 * v);
-    float* t2 = cv.take<float>(3 * v);
+    Carver cv(workspace);
+    const auto [t1, t2, sync] = ic_layout(cv, v);
     if (iters == 0) {
         if (o1 != f1) (void)hipMemcpyAsync(o1, f1, bytes, hipMemcpyDeviceToDevice, s);
         if (o2 != f2) (void)hipMemcpyAsync(o2, f2, bytes, hipMemcpyDeviceToDevice, s);
         return check_last("inverse_consistency");
     }
     if (options().ic_fused && iters >= 2 && v * 3 < ((size_t)1 << 30)) {
-        ICSync* sync = cv.take<ICSync>(1);
         if (hipMemsetAsync(sync, 0, sizeof(ICSync), s) != hipSuccess) return fail(CVX_ERR_LAUNCH, "inverse_consistency: memset failed");
         static std::atomic<unsigned> turn{0};
         const int xcd = (int)(turn.fetch_add(1) & 7u);                     // concurrent pairs (register_pairs streams) take different XCDs

@@ -118,10 +118,16 @@ bool corr_cert_supported(int C, int h, int w, int d, int hw) {
     const size_t total = (size_t)g.off_M[g.ntype - 1] + (size_t)g.chanM * C;
     return total < ((size_t)1 << 31) && (size_t)h * w * d * 4 < ((size_t)1 << 31);
 }
-size_t corr_cert_workspace_bytes(int C, int h, int w, int d, int hw) {
-    const CCGeom g = cc_geom(C, h, w, d, hw);
-    return (size_t)g.stage_bytes + 512 + 32 * 1024;          // (+ the residency census of option cc_debug)
+// the staging copies, then the residency census of option cc_debug (4096 words); the layout starts at the first 256-byte aligned ADDRESS of
+// the workspace (up to 255 bytes in: + 256 in the query)
+struct CCWs { char* stage; unsigned long long* census; };
+static CCWs cc_layout(Carver& cv, const CCGeom& g) {
+    CCWs c;
+    c.stage = cv.take<char>(g.stage_bytes);
+    c.census = cv.take<unsigned long long>(4096);
+    return c;
 }
+size_t corr_cert_workspace_bytes(int C, int h, int w, int d, int hw) { Carver m; cc_layout(m, cc_geom(C, h, w, d, hw)); return 256 + ws_query(m); }
 
 // ---- staging copies: Fp [C][h][w][4 FQ] (zeros behind d); Mp_t [C][HQ][WQ][4 MQ] per tile type t with element i = the moving
 // feature at shift index tstart[t] + i, i.e. at column tstart[t] + i - hw (zero outside the volume); rows / planes shifted by hw ------
@@ -668,7 +674,9 @@ int launch_corr_cert(const float* fix, const float* mov, int C, int h, int w, in
     if (!corr_cert_supported(C, h, w, d, hw)) return fail(CVX_ERR_UNSUPPORTED, "correlate (certified fast): geometry outside the kernel's range");
     if (workspace_bytes < corr_cert_workspace_bytes(C, h, w, d, hw)) return fail(CVX_ERR_WORKSPACE, "correlate (certified fast): workspace too small");
     const CCGeom g = cc_geom(C, h, w, d, hw);
-    char* stage = reinterpret_cast<char*>(align_up(reinterpret_cast<uintptr_t>(workspace), 256));
+    Carver cv(reinterpret_cast<void*>(align_up(reinterpret_cast<uintptr_t>(workspace), 256)));
+    const CCWs c = cc_layout(cv, g);
+    char* stage = c.stage;
     const size_t nprep = std::max((size_t)C * g.HQ * g.WQ * g.MQ, (size_t)C * h * w * g.FQ);
     hipLaunchKernelGGL(k_cc_prep, dim3((unsigned)cdiv64((int64_t)nprep, 256)), dim3(256), 0, s, fix, mov, g, stage);
     CCKern k{};
@@ -683,7 +691,7 @@ int launch_corr_cert(const float* fix, const float* mov, int C, int h, int w, in
     for (int i = 0; i < CC_MAXT; ++i) k.off_M[i] = g.off_M[i];
     k.chanF = g.chanF; k.chanM = g.chanM; k.stage_bytes = g.stage_bytes;
     k.dbg = (int)options().cc_debug;
-    k.census = options().cc_debug ? reinterpret_cast<unsigned long long*>(stage + align_up((size_t)g.stage_bytes, 256)) : nullptr;
+    k.census = options().cc_debug ? c.census : nullptr;
     const size_t lds = cc_lds_bytes(g);
     const dim3 block(2 * g.wps * 64 + CC_LOADER_THREADS);
 #define CC_LAUNCH(CT, MAXT)                                                                         \

@@ -258,24 +258,27 @@ static bool certfast_use_unfused(int C, int h, int w, int d, int hw) {
     const bool role_good = corr_fused_supported(C, h, w, d, hw) && C <= 32 && corr_fused_items(C, h, w, d, hw) >= 384 && !corr_fused_tiled(C, h, w, d, hw);
     return !role_good;
 }
-static size_t certfast_unfused_workspace(int C, int h, int w, int d, int hw) {
+// the round-1 kernels' workspace: padded copies, raw SSDs, then (the exact operator) the argmin keys
+struct Round1Ws { float *Fp, *Mp, *raw; unsigned long long* keys; };
+static Round1Ws round1_layout(Carver& cv, int C, int h, int w, int d, int hw, bool keys) {
     const CorrGeom g = corr_geom(C, h, w, d, hw);
-    const size_t K = (size_t)g.n * g.n * g.n;
-    size_t used = 0;
-    used = carve_size(used, sizeof(float) * (size_t)C * h * w * g.px);
-    used = carve_size(used, sizeof(float) * (size_t)C * g.hq * g.wq * g.dq);
-    used = carve_size(used, sizeof(float) * K * h * w * g.px);
-    return used + 256;
+    Round1Ws r{};
+    r.Fp = cv.take<float>((size_t)C * h * w * g.px);
+    r.Mp = cv.take<float>((size_t)C * g.hq * g.wq * g.dq);
+    r.raw = cv.take<float>((size_t)g.n * g.n * g.n * h * w * g.px);
+    if (keys) r.keys = cv.take<unsigned long long>((size_t)h * w * d);
+    return r;
+}
+static size_t certfast_unfused_workspace(int C, int h, int w, int d, int hw) {
+    Carver m; round1_layout(m, C, h, w, d, hw, false); return ws_query(m);
 }
 static int launch_corr_certfast_unfused(const float* fix, const float* mov, int C, int h, int w, int d, int hw, float* ssdu, void* workspace, size_t workspace_bytes,
                                         hipStream_t s) {
     if (workspace_bytes < certfast_unfused_workspace(C, h, w, d, hw)) return fail(CVX_ERR_WORKSPACE, "correlate (certified-fast, two kernels): workspace too small");
     const CorrGeom g = corr_geom(C, h, w, d, hw);
     const size_t K = (size_t)g.n * g.n * g.n;
-    Carver cv(workspace, workspace_bytes);
-    float* Fp = cv.take<float>((size_t)C * h * w * g.px);
-    float* Mp = cv.take<float>((size_t)C * g.hq * g.wq * g.dq);
-    float* raw = cv.take<float>(K * h * w * g.px);
+    Carver cv(workspace);
+    const auto [Fp, Mp, raw, no_keys] = round1_layout(cv, C, h, w, d, hw, false);
     const size_t nprep = (size_t)C * g.hq * g.wq * g.dq;
     hipLaunchKernelGGL(k_corr_prep, dim3((unsigned)cdiv64((int64_t)nprep, 256)), dim3(256), 0, s, fix, mov, g, Fp, Mp);
     corr_call_prep_hook(s);
@@ -311,8 +314,7 @@ size_t corr_certfast_workspace_bytes(int C, int h, int w, int d, int hw) {
     const size_t a = corr_cert_supported(C, h, w, d, hw) ? corr_cert_workspace_bytes(C, h, w, d, hw) : 0;
     const size_t b = corr_fused_supported(C, h, w, d, hw) ? corr_fused_workspace_bytes(C, h, w, d, hw) : 0;
     const size_t c = certfast_unfused_ok(C, h, w, d, hw) ? certfast_unfused_workspace(C, h, w, d, hw) : 0;
-    const size_t m = a > b ? a : b;
-    return align_up(m > c ? m : c, 256);
+    return std::max({a, b, c});
 }
 int launch_corr_certfast(const float* fix, const float* mov, int C, int h, int w, int d, int hw, float* ssdu, void* workspace, size_t workspace_bytes,
                          hipStream_t s) {
@@ -336,25 +338,28 @@ bool cvx::corr_use_unfused(int C, int h, int w, int d, int hw, bool variant) {
     return corr_box2_supported(h, w, d, g.px) && (size_t)g.n * g.n * g.n * h * w * g.px * sizeof(float) <= ((size_t)2 << 30);
 }
 
-static size_t correlate_workspace_exact(int C, int h, int w, int d, int disp_hw);
-extern "C" size_t cvx_correlate_workspace_bytes(int C, int h, int w, int d, int disp_hw) {
-    // (the certified-fast variant, cvx_corr_opts.fast = 2, stages its own padded copies)
-    const size_t exact = correlate_workspace_exact(C, h, w, d, disp_hw);
-    const size_t cert = corr_certfast_supported(C, h, w, d, disp_hw) ? corr_certfast_workspace_bytes(C, h, w, d, disp_hw) + corr_certify_workspace_bytes(C, h, w, d, disp_hw, true) + 512 : 0;
-    return exact > cert ? exact : cert;
+// cvx_correlate_ex_f32's workspace holds one of three layouts: the fused kernel's workspace + the argmin keys; the round-1 kernels'
+// (Round1Ws); or (fast = 2) the certified-fast volume's workspace + the plain certified argmin's.  The query is the largest that applies.
+struct PartsWs { void* a; size_t a_bytes; void* b; size_t b_bytes; };
+static PartsWs parts_layout(Carver& cv, size_t a_bytes, size_t b_bytes) {
+    PartsWs p{nullptr, a_bytes, nullptr, b_bytes};
+    p.a = cv.take<char>(a_bytes);
+    p.b = cv.take<char>(b_bytes);
+    return p;
 }
-static size_t correlate_workspace_exact(int C, int h, int w, int d, int disp_hw) {
-    const size_t fused = corr_fused_supported(C, h, w, d, disp_hw)
-                             ? carve_size(corr_fused_workspace_bytes(C, h, w, d, disp_hw), sizeof(unsigned long long) * (size_t)h * w * d) + 256 : 0;
-    if (fused && !corr_use_unfused(C, h, w, d, disp_hw, false)) return fused;         // fused kernel: no raw intermediate
-    const CorrGeom g = corr_geom(C, h, w, d, disp_hw);
-    const size_t K = (size_t)g.n * g.n * g.n;
-    size_t used = 0;
-    used = carve_size(used, sizeof(float) * (size_t)C * h * w * g.px);            // Fp
-    used = carve_size(used, sizeof(float) * (size_t)C * g.hq * g.wq * g.dq);      // Mp
-    used = carve_size(used, sizeof(float) * K * h * w * g.px);                    // raw
-    used = carve_size(used, sizeof(unsigned long long) * (size_t)h * w * d);      // argmin keys
-    return (used + 256 > fused ? used + 256 : fused);                             // (the variants of cvx_correlate_ex_f32 take the fused kernel)
+static PartsWs fused_keys_layout(Carver& cv, int C, int h, int w, int d, int hw) {
+    return parts_layout(cv, corr_fused_workspace_bytes(C, h, w, d, hw), sizeof(unsigned long long) * (size_t)h * w * d);
+}
+static PartsWs certified_layout(Carver& cv, int C, int h, int w, int d, int hw) {
+    return parts_layout(cv, corr_certfast_workspace_bytes(C, h, w, d, hw), corr_certify_workspace_bytes(C, h, w, d, hw, true));
+}
+extern "C" size_t cvx_correlate_workspace_bytes(int C, int h, int w, int d, int disp_hw) {
+    Carver fused, round1, cert;
+    const bool fused_ok = corr_fused_supported(C, h, w, d, disp_hw);
+    if (fused_ok) fused_keys_layout(fused, C, h, w, d, disp_hw);
+    if (!fused_ok || corr_use_unfused(C, h, w, d, disp_hw, false)) round1_layout(round1, C, h, w, d, disp_hw, true);
+    if (corr_certfast_supported(C, h, w, d, disp_hw)) certified_layout(cert, C, h, w, d, disp_hw);
+    return std::max({ws_query(fused), ws_query(round1), ws_query(cert)});
 }
 
 extern "C" int cvx_correlate_f32(const float* fix, const float* mov, int C, int h, int w, int d, int disp_hw, float* ssd,
@@ -382,21 +387,20 @@ extern "C" int cvx_correlate_ex_f32(const float* fix, const float* mov, int C, i
         // is the reference's argmin (first minimum of the EXACT volume), certified from the fast one and resolved exactly where it cannot be
         if (f16) return fail(CVX_ERR_UNSUPPORTED, "cvx_correlate_ex_f32: the certified-fast volume is float32");
         if (!corr_certfast_supported(C, h, w, d, disp_hw)) return fail(CVX_ERR_UNSUPPORTED, "cvx_correlate_ex_f32: certified-fast correlation not built for this geometry");
-        const size_t cws = corr_certfast_workspace_bytes(C, h, w, d, disp_hw);
-        int rc = launch_corr_certfast(fix, mov, C, h, w, d, disp_hw, ssd, workspace, cws, s);
+        Carver cv(workspace);
+        const PartsWs c = certified_layout(cv, C, h, w, d, disp_hw);
+        int rc = launch_corr_certfast(fix, mov, C, h, w, d, disp_hw, ssd, c.a, c.a_bytes, s);
         if (rc || !argmin) return rc;
-        return corr_certified_argmin(ssd, fix, mov, C, h, w, d, disp_hw, argmin, static_cast<char*>(workspace) + align_up(cws, 256),
-                                     corr_certify_workspace_bytes(C, h, w, d, disp_hw, true), s);
+        return corr_certified_argmin(ssd, fix, mov, C, h, w, d, disp_hw, argmin, c.b, c.b_bytes, s);
     }
     const bool variant = cost != 0 || n_box != 2 || fast || f16;
     if (!corr_use_unfused(C, h, w, d, disp_hw, variant)) {
-        const size_t fws = corr_fused_workspace_bytes(C, h, w, d, disp_hw);
-        int rc = launch_corr_fused(fix, mov, C, h, w, d, disp_hw, cost, n_box, fast, f16, ssd, workspace, fws, s);
+        Carver cv(workspace);
+        const PartsWs f = fused_keys_layout(cv, C, h, w, d, disp_hw);
+        int rc = launch_corr_fused(fix, mov, C, h, w, d, disp_hw, cost, n_box, fast, f16, ssd, f.a, f.a_bytes, s);
         if (rc) return rc;
-        if (argmin) {
-            unsigned long long* keys = reinterpret_cast<unsigned long long*>(static_cast<char*>(workspace) + align_up(fws, 256));
-            return launch_argmin(ssd, f16 == 2, nullptr, nullptr, 0.0f, false, (int)K, (size_t)h * w * d, keys, argmin, s);
-        }
+        if (argmin)
+            return launch_argmin(ssd, f16 == 2, nullptr, nullptr, 0.0f, false, (int)K, (size_t)h * w * d, static_cast<unsigned long long*>(f.b), argmin, s);
         return CVX_OK;
     }
     if (variant)
@@ -404,11 +408,8 @@ extern "C" int cvx_correlate_ex_f32(const float* fix, const float* mov, int C, i
     if (disp_hw > 8) return fail(CVX_ERR_UNSUPPORTED, "cvx_correlate_f32: disp_hw %d > 8 needs the fused kernel (option corr_unfused is set, or the grid is outside its range: the fused kernel covers rows of d <= ~1270 voxels when the plane has w <= 320 / ceil((d + 6) / 4) rows, else (y tiles) d <= ~250)", disp_hw);
     if (!corr_box2_supported(h, w, d, g.px))
         return fail(CVX_ERR_UNSUPPORTED, "cvx_correlate_f32: coarse rows of %d voxels are too long for the LDS box kernel", d);
-    Carver cv(workspace, workspace_bytes);
-    float* Fp = cv.take<float>((size_t)C * h * w * g.px);
-    float* Mp = cv.take<float>((size_t)C * g.hq * g.wq * g.dq);
-    float* raw = cv.take<float>(K * h * w * g.px);
-    unsigned long long* keys = cv.take<unsigned long long>((size_t)h * w * d);
+    Carver cv(workspace);
+    const auto [Fp, Mp, raw, keys] = round1_layout(cv, C, h, w, d, disp_hw, true);
 
     const size_t nprep = (size_t)C * g.hq * g.wq * g.dq;   // >= nF
     hipLaunchKernelGGL(k_corr_prep, dim3((unsigned)cdiv64((int64_t)nprep, 256)), dim3(256), 0, s, fix, mov, g, Fp, Mp);

@@ -521,15 +521,17 @@ int corr_fused_items(int C, int h, int w, int d, int hw) {
 
 bool corr_fused_tiled(int C, int h, int w, int d, int hw) { return cf_geom(C, h, w, d, hw).tiled != 0; }
 
-size_t corr_fused_workspace_bytes(int C, int h, int w, int d, int hw) {
-    const CFGeom g = cf_geom(C, h, w, d, hw);
-    size_t used = 0;
-    used = carve_size(used, sizeof(float) * (size_t)C * h * w * g.RS);            // Fp
-    used = carve_size(used, sizeof(float) * ((size_t)C * g.hq * g.wq * g.dq + 8));  // Mp
-    used = carve_size(used, sizeof(float) * 32 * g.n);                             // tail values
-    used = carve_size(used, 32 * ((size_t)g.n * g.n * g.ng * (g.nyt > 0 ? g.nyt : 1) + 8));  // residency census (CVX_CF_CENSUS; + 8: the 512 slots of option cf_map)
-    return used + 256;
+// one direction's padded feature copies and tail values, then the residency census of option cf_census (+ 8: the 512 slots of option cf_map)
+struct CFWs { float *Fp, *Mp, *tail; unsigned long long* census; };
+static CFWs cf_layout(Carver& cv, const CFGeom& g, int C, int h, int w) {
+    CFWs f;
+    f.Fp = cv.take<float>((size_t)C * h * w * g.RS);
+    f.Mp = cv.take<float>((size_t)C * g.hq * g.wq * g.dq + 8);
+    f.tail = cv.take<float>((size_t)32 * g.n);
+    f.census = cv.take<unsigned long long>((size_t)4 * (g.n * g.n * g.ng * (g.nyt > 0 ? g.nyt : 1) + 8));
+    return f;
 }
+size_t corr_fused_workspace_bytes(int C, int h, int w, int d, int hw) { Carver m; cf_layout(m, cf_geom(C, h, w, d, hw), C, h, w); return ws_query(m); }
 
 // prep / tail kernels of correlate.hip
 void launch_corr_prep_generic(const float* fix, const float* mov, int C, int h, int w, int d, int hw, int px, int PL, int dq, float* Fp,
@@ -582,23 +584,17 @@ int launch_corr_fused_dual(const float* fix, const float* mov, int C, int h, int
     if (fast == 2 && f16) return fail(CVX_ERR_UNSUPPORTED, "correlate: the unscaled fast volume is float32");
     if (f16 && (cost != 0 || n_box != 2)) return fail(CVX_ERR_UNSUPPORTED, "correlate: fp16 storage exists for the SSD cost with two boxes only");
     if (f16 < 0 || f16 > 2) return fail(CVX_ERR_INVALID_ARG, "correlate: f16 must be 0, 1 or 2");
-    Carver cv(workspace, workspace_bytes);
-    float* Fp = cv.take<float>((size_t)C * h * w * g.RS);
-    float* Mp = cv.take<float>((size_t)C * g.hq * g.wq * g.dq + 8);
-    float* tail = cv.take<float>((size_t)32 * g.n);
-    unsigned long long* census_buf = cv.take<unsigned long long>((size_t)4 * (g.n * g.n * g.ng * g.nyt + 8));
+    if (ssd_rev && !workspace_rev) return fail(CVX_ERR_WORKSPACE, "correlate (fused, both directions): second workspace missing");
+    Carver cv(workspace), cr(workspace_rev);
+    const CFWs f = cf_layout(cv, g, C, h, w), r = cf_layout(cr, g, C, h, w);    // (the reverse direction's workspace: same layout)
+    float *Fp = f.Fp, *Mp = f.Mp, *tail = f.tail;
     launch_corr_prep_generic(fix, mov, C, h, w, d, hw, g.RS, hw, g.dq, Fp, Mp, s);
     if (g.ntail > 0 && !fast) launch_corr_tail_compact(fix, mov, C, h, w, d, hw, cost, tail, s);
     CFSecond two = {nullptr, nullptr, nullptr, nullptr, 0};
     if (ssd_rev) {
-        if (!workspace_rev) return fail(CVX_ERR_WORKSPACE, "correlate (fused, both directions): second workspace missing");
-        Carver cr(workspace_rev, workspace_bytes);
-        float* Fp2 = cr.take<float>((size_t)C * h * w * g.RS);
-        float* Mp2 = cr.take<float>((size_t)C * g.hq * g.wq * g.dq + 8);
-        float* tail2 = cr.take<float>((size_t)32 * g.n);
-        launch_corr_prep_generic(mov, fix, C, h, w, d, hw, g.RS, hw, g.dq, Fp2, Mp2, s);
-        if (g.ntail > 0 && !fast) launch_corr_tail_compact(mov, fix, C, h, w, d, hw, cost, tail2, s);
-        two.Fp = Fp2; two.Mp = Mp2; two.tail = tail2; two.ssd = ssd_rev;
+        launch_corr_prep_generic(mov, fix, C, h, w, d, hw, g.RS, hw, g.dq, r.Fp, r.Mp, s);
+        if (g.ntail > 0 && !fast) launch_corr_tail_compact(mov, fix, C, h, w, d, hw, cost, r.tail, s);
+        two.Fp = r.Fp; two.Mp = r.Mp; two.tail = r.tail; two.ssd = ssd_rev;
     }
     const CFSecond* sec = ssd_rev ? &two : nullptr;
     if (t_after_prep) t_after_prep(s);
@@ -606,7 +602,7 @@ int launch_corr_fused_dual(const float* fix, const float* mov, int C, int h, int
     gl.prio = (int)options().cf_prio;
     // (pairs of a slot: 2 x (256 - nn) >= nn first groups)
     gl.colocate = (options().cf_map == 1 && !ssd_rev && !g.tiled && g.ng == 3 && g.gs == 4 && g.n * g.n <= 256 && 2 * (256 - g.n * g.n) >= g.n * g.n) ? 1 : 0;
-    gl.dbg = (options().cf_census && !ssd_rev) ? census_buf : nullptr;      // debugging aid: per-workgroup start / end / placement in the workspace
+    gl.dbg = (options().cf_census && !ssd_rev) ? f.census : nullptr;      // debugging aid: per-workgroup start / end / placement in the workspace
     if (fast == 2) cf_launch<1 + 32>(gl, Fp, Mp, tail, ssd, s, sec);
     else if (fast && f16 == 2) cf_launch<1 + 8 + 16>(gl, Fp, Mp, tail, ssd, s, sec);
     else if (fast && f16) cf_launch<9>(gl, Fp, Mp, tail, ssd, s, sec);

@@ -42,20 +42,18 @@ static inline void ensure_dynamic_lds(KernelT kernel, size_t bytes, size_t& gran
     }
 }
 
-// bump allocator over the caller's workspace (256-byte aligned carves)
+// bump allocator over a workspace (256-byte aligned carves).  Every workspace has ONE layout function over a Carver: the launcher runs it
+// over its memory, the size query over Carver() -- a measuring carver: null pointers, `used` counts the bytes -- and returns ws_query()
 struct Carver {
-    char* base;
-    size_t size, used;
-    Carver(void* p, size_t n) : base(static_cast<char*>(p)), size(n), used(0) {}
-    template <typename T>
-    T* take(size_t count) {
-        size_t off = align_up(used, 256);
-        used = off + count * sizeof(T);
-        return reinterpret_cast<T*>(base + off);
-    }
-    bool ok() const { return used <= size && (base != nullptr || used == 0); }
+    char* base = nullptr;
+    size_t used = 0;
+    Carver() = default;
+    explicit Carver(void* p) : base(static_cast<char*>(p)) {}
+    size_t take_bytes(size_t bytes) { const size_t off = align_up(used, 256); used = off + bytes; return off; }     // offset of the carve
+    template <typename T> T* take(size_t count) { const size_t off = take_bytes(count * sizeof(T)); return base ? reinterpret_cast<T*>(base + off) : nullptr; }
 };
-static inline size_t carve_size(size_t used, size_t bytes) { return align_up(used, 256) + bytes; }
+// a size query's value: the measured carves + 256 bytes of slack behind the last one (0: the layout takes nothing)
+static inline size_t ws_query(const Carver& m) { return m.used ? m.used + 256 : 0; }
 
 // ---- run-time switches between kernel variants ---------------------------------------------------------------------------------
 // One table per context (cvx_context_*); the default context is initialised once from the environment (CVX_<NAME IN CAPITALS>, e.g.
@@ -363,8 +361,9 @@ int launch_smoother(const float* in, float* out, float* tmp, int C, int H, int W
                     hipStream_t s);
 // (ssd: float32 cost volume, or half precision when f16 -- fp16 storage)
 int launch_argmin_keys(const void* ssd, bool f16, int K, size_t v, unsigned long long* keys, bool arm, hipStream_t s);   // arm = false: the caller set the keys to all ones
-// the two alternating list lengths of the pruned passes inside a coupled-convex workspace (same carve-up as coupled_core)
-int* coupled_ws_counts(void* workspace, size_t workspace_bytes, int h, int w, int d, int disp_hw);
+// the coupled-convex workspace: three key buffers, winners, minima, the pruned passes' work list and its two alternating lengths
+struct CoupledWs { unsigned long long* keys[3]; int* idx; float* smin; unsigned long long* list; int* counts; };
+CoupledWs coupled_layout(Carver& cv, int h, int w, int d, int disp_hw);
 int launch_argmin(const void* ssd, bool f16, const float* mesh, const float* u, float coef, bool coupled, int K, size_t v,
                   unsigned long long* keys, int64_t* argmin_out, hipStream_t s);
 // out = interp(in * pre_mul) / post_div   (pre_mul, post_div = 1 -> plain F.interpolate)
@@ -409,12 +408,13 @@ int adam_run_impl(const float* F2, const float* M2, int C, int h, int w, int d, 
                   float* grad_out, const int* snapshot_iters_host, int n_snap, float* snapshots, const cvx_smoother* sm,
                   bool keep_state, bool f16_features, int fast, void* workspace, size_t workspace_bytes, void* stream,
                   bool features_are_records = false);   // fast: 0 exact, 1 fast, 2 fast_all; features_are_records: F2 / M2 already hold the chunked records
+size_t adam_record_floats(int C, size_t V);            // floats of one feature record of the Adam loop: [CP/4][V + 1][4], CP = C rounded up to 4
 // convex.hip: coupled convex regularisation behind cvx_coupled_convex_f32 (argmin_is_exact: see there)
 int coupled_convex_impl(const void* ssd, bool f16, const int64_t* argmin, const float* mesh, int h, int w, int d, int disp_hw, float* out,
                         bool argmin_is_exact, void* workspace, size_t workspace_bytes, void* stream);
 int coupled_convex_dual_impl(const void* ssdA, const int64_t* argminA, float* outA, void* wsA, const void* ssdB, bool f16, const int64_t* argminB,
                              float* outB, void* wsB, const float* mesh, int h, int w, int d, int disp_hw, size_t workspace_bytes,
-                             void* stream, bool counts_zeroed = false);   // counts_zeroed: the caller cleared coupled_ws_counts of both workspaces
+                             void* stream, bool counts_zeroed = false);   // counts_zeroed: the caller cleared CoupledWs::counts of both workspaces
 // mind.hip: MIND-SSC delivered only through its stride poolings (pipeline path, no full-resolution descriptor)
 bool mind_pooled_supported(int H, int W, int D, int g1, int g2);
 int launch_mind_pooled(const float* img, int H, int W, int D, int radius, int dilation, int g1, float* out1, int g2, float* out2,

@@ -380,10 +380,9 @@ __global__ __launch_bounds__(1024) void k_hist_order_stats(const unsigned long l
 
 using namespace cvx;
 
-extern "C" size_t cvx_feature_transform_workspace_bytes(int H, int W, int D) {
-    // per line: 3*len coordinates + len stack entries, for the pass with the largest (lines x length) = 4 * V ints
-    return 256 + sizeof(int) * 4 * (size_t)H * W * D;
-}
+// per line: 3*len coordinates + len stack entries, for the pass with the largest (lines x length) = 4 * V ints
+static int* ft_layout(Carver& cv, int H, int W, int D) { return cv.take<int>(4 * (size_t)H * W * D); }
+extern "C" size_t cvx_feature_transform_workspace_bytes(int H, int W, int D) { Carver m; ft_layout(m, H, W, D); return ws_query(m); }
 
 extern "C" int cvx_feature_transform_i32(const float* obj, int H, int W, int D, int* feat, void* workspace, size_t workspace_bytes,
                                          void* stream) {
@@ -392,9 +391,9 @@ extern "C" int cvx_feature_transform_i32(const float* obj, int H, int W, int D, 
     if (workspace_bytes < cvx_feature_transform_workspace_bytes(H, W, D))
         return fail(CVX_ERR_WORKSPACE, "cvx_feature_transform_i32: workspace too small");
     hipStream_t s = as_stream(stream);
-    Carver cv(workspace, workspace_bytes);
+    Carver cv(workspace);
     const size_t V = (size_t)H * W * D;
-    int* scr = cv.take<int>(4 * V);
+    int* scr = ft_layout(cv, H, W, D);
     hipLaunchKernelGGL(k_ft_init, dim3((unsigned)cdiv64((int64_t)V, 256)), dim3(256), 0, s, obj, H, W, D, feat);
     hipLaunchKernelGGL(k_ft_pass<0>, dim3(cdiv(W * D, 128)), dim3(128), 0, s, feat, H, W, D, scr);
     hipLaunchKernelGGL(k_ft_pass<1>, dim3(cdiv(H * D, 128)), dim3(128), 0, s, feat, H, W, D, scr);
@@ -583,10 +582,9 @@ __global__ __launch_bounds__(256) void k_edt_envelope_tile(int* __restrict__ vol
     }
 }
 
-extern "C" size_t cvx_edt_squared_workspace_bytes(int batch, int H, int W, int D) {
-    // per line: 2 stack entries + 1 result per element, for the pass with the largest (lines x length) = 3 * V ints per volume
-    return 256 + sizeof(int) * 3 * (size_t)(batch > 0 ? batch : 1) * H * W * D;
-}
+// per line: 2 stack entries + 1 result per element, for the pass with the largest (lines x length) = 3 * V ints per volume
+static int* edt_layout(Carver& cv, int batch, int H, int W, int D) { return cv.take<int>(3 * (size_t)batch * H * W * D); }
+extern "C" size_t cvx_edt_squared_workspace_bytes(int batch, int H, int W, int D) { Carver m; edt_layout(m, batch > 0 ? batch : 1, H, W, D); return ws_query(m); }
 
 // `batch` independent volumes [batch][H][W][D] in one set of launches (one thread per line: a single 160 x 192 x 224 volume leaves
 // most of the GPU idle in the envelope passes)
@@ -612,8 +610,8 @@ static int edt_squared_impl(const float* obj, const EdtLabels* labels, int batch
     CVX_REQUIRE((double)batch * H * W * D < 2147483647.0 * 0.3, "cvx_edt_squared_i32: batch too large");
     if (workspace_bytes < cvx_edt_squared_workspace_bytes(batch, H, W, D)) return fail(CVX_ERR_WORKSPACE, "cvx_edt_squared_i32: workspace too small");
     hipStream_t s = as_stream(stream);
-    Carver cv(workspace, workspace_bytes);
-    int* scr = cv.take<int>(3 * (size_t)batch * H * W * D);
+    Carver cv(workspace);
+    int* scr = edt_layout(cv, batch, H, W, D);
     const int nrows = batch * H * W;
     if (labels) hipLaunchKernelGGL(k_edt_rows<true>, dim3((unsigned)cdiv(nrows, 4)), dim3(256), 0, s, obj, nrows, D, d2, *labels, H * W);
     else hipLaunchKernelGGL(k_edt_rows<false>, dim3((unsigned)cdiv(nrows, 4)), dim3(256), 0, s, obj, nrows, D, d2, EdtLabels{}, H * W);

@@ -741,51 +741,66 @@ static int mind_launch_r(const float* img, int H, int W, int D, int dil, MindSta
     return check_last("mindssc");
 }
 
+// the MIND workspace: min / max partials and the statistics, then either the block list of the single pass (window ga > 0) or the
+// buffers of the reference-bits mean (T = option mind_mean_threads > 0): variance volume, thread slots, three cascade levels
+struct MindWs {
+    float* part; MindStats* st; unsigned* blk; size_t nblk;
+    float *var, *slots, *B0, *B1, *B2; int threads; bool two_pass; long long nt, chunk, rows, s0, s1, s2;
+};
+static MindWs mind_layout(Carver& cv, int H, int W, int D, int ga, long long T) {
+    MindWs m{};
+    m.part = cv.take<float>(2 * 1024);
+    m.st = cv.take<MindStats>(1);
+    if (ga > 0) {
+        m.nblk = (size_t)cdiv(H, ga) * cdiv(W, ga) * cdiv(D, ga);
+        m.blk = cv.take<unsigned>(3 * m.nblk);
+        return m;
+    }
+    if (T <= 0) return m;
+    const size_t V = (size_t)H * W * D;
+    m.threads = (int)(T > 1024 ? 1024 : T);
+    m.two_pass = V >= 32768 && m.threads > 1;
+    m.nt = 1; m.chunk = (long long)V;
+    if (m.two_pass) {
+        m.nt = ((long long)V + 32767) / 32768;
+        if (m.nt > m.threads) m.nt = m.threads;
+        m.chunk = ((long long)V + m.nt - 1) / m.nt;
+    }
+    // level buffers: at most nv4 / 16, / 256, / 4096 rows of 32 floats per chunk
+    m.rows = m.chunk / 32 + 1;
+    m.s0 = (m.rows / 16 + 1) * 32; m.s1 = (m.rows / 256 + 1) * 32; m.s2 = (m.rows / 4096 + 1) * 32;
+    m.var = cv.take<float>(V); m.slots = cv.take<float>(1024);
+    m.B0 = cv.take<float>((size_t)(m.s0 * m.nt)); m.B1 = cv.take<float>((size_t)(m.s1 * m.nt)); m.B2 = cv.take<float>((size_t)(m.s2 * m.nt));
+    return m;
+}
+
 // min/max -> split grids -> stencil pass: raw patch SSDs in `raw` [12][V] (final channel order), statistics in *st
 static int mind_stencil(const float* img, int H, int W, int D, int radius, int dilation, float* raw, void* workspace,
                         size_t workspace_bytes, MindStats** st_out, hipStream_t s, const MindRawLayout& lay = MindRawLayout{0, 0, 0, 0, 0}) {
-    Carver cv(workspace, workspace_bytes);
-    float* part = cv.take<float>(2 * 1024);
-    MindStats* st = cv.take<MindStats>(1);
-    *st_out = st;
+    Carver cv(workspace);
+    const long long T = options().mind_mean_threads;
+    const MindWs m = mind_layout(cv, H, W, D, 0, T);
+    MindStats* st = *st_out = m.st;
     const size_t V = (size_t)H * W * D;
     const int nb = (int)(V / 4096 + 1 < 1024 ? V / 4096 + 1 : 1024);
-    hipLaunchKernelGGL(k_minmax_partial, dim3(nb), dim3(256), 0, s, img, V, part);
-    hipLaunchKernelGGL(k_mind_stats_init, dim3(1), dim3(256), 0, s, part, nb, (double)V, st);
+    hipLaunchKernelGGL(k_minmax_partial, dim3(nb), dim3(256), 0, s, img, V, m.part);
+    hipLaunchKernelGGL(k_mind_stats_init, dim3(1), dim3(256), 0, s, m.part, nb, (double)V, st);
     int rc;
     switch (radius) {
         case 1: rc = mind_launch_r<1>(img, H, W, D, dilation, st, raw, s, lay); break;
         case 2: rc = mind_launch_r<2>(img, H, W, D, dilation, st, raw, s, lay); break;
         default: rc = mind_launch_r<3>(img, H, W, D, dilation, st, raw, s, lay); break;
     }
-    const long long T = options().mind_mean_threads;
     if (rc || T <= 0) return rc;
     // reference-bits mode: torch's own mean instead of the exactly rounded one
-    const int threads = (int)(T > 1024 ? 1024 : T);
-    float* var = cv.take<float>(V);
-    float* slots = cv.take<float>(1024);
-    const bool two_pass = V >= 32768 && threads > 1;
-    long long nt = 1, chunk = (long long)V;
-    if (two_pass) {
-        nt = ((long long)V + 32767) / 32768;
-        if (nt > threads) nt = threads;
-        chunk = ((long long)V + nt - 1) / nt;
-    }
-    // level buffers: at most nv4 / 16, / 256, / 4096 rows of 32 floats per chunk
-    const long long rows = chunk / 32 + 1;
-    const long long s0 = (rows / 16 + 1) * 32, s1 = (rows / 256 + 1) * 32, s2 = (rows / 4096 + 1) * 32;
-    float* B0 = cv.take<float>((size_t)(s0 * nt));
-    float* B1 = cv.take<float>((size_t)(s1 * nt));
-    float* B2 = cv.take<float>((size_t)(s2 * nt));
-    if (!cv.ok()) return fail(CVX_ERR_WORKSPACE, "mindssc: workspace too small for mind_mean_threads (query the size after setting the option)");
-    hipLaunchKernelGGL(k_mind_var, dim3((unsigned)cdiv64((int64_t)V, 256)), dim3(256), 0, s, raw, V, var);
-    if (two_pass) (void)hipMemsetAsync(slots, 0, 1024 * sizeof(float), s);              // unused slots keep the identity
+    hipLaunchKernelGGL(k_mind_var, dim3((unsigned)cdiv64((int64_t)V, 256)), dim3(256), 0, s, raw, V, m.var);
+    if (m.two_pass) (void)hipMemsetAsync(m.slots, 0, 1024 * sizeof(float), s);              // unused slots keep the identity
     auto blocks = [](long long nrows) { return (unsigned)((nrows * 32 + 255) / 256 > 0 ? (nrows * 32 + 255) / 256 : 1); };
-    hipLaunchKernelGGL(k_torch_sum_level<0>, dim3(blocks(rows / 16 + 1), (unsigned)nt), dim3(256), 0, s, var, B0, (long long)V, chunk, 0ll, s0);
-    hipLaunchKernelGGL(k_torch_sum_level<1>, dim3(blocks(rows / 256 + 1), (unsigned)nt), dim3(256), 0, s, B0, B1, (long long)V, chunk, s0, s1);
-    hipLaunchKernelGGL(k_torch_sum_level<2>, dim3(blocks(rows / 4096 + 1), (unsigned)nt), dim3(256), 0, s, B1, B2, (long long)V, chunk, s1, s2);
-    hipLaunchKernelGGL(k_torch_sum_chunks, dim3((unsigned)nt), dim3(64), 0, s, var, B0, B1, B2, (long long)V, chunk, s0, s1, s2, slots);
-    hipLaunchKernelGGL(k_torch_sum_final, dim3(1), dim3(1), 0, s, slots, threads, two_pass ? 1 : 0, (long long)V, st);
+    hipLaunchKernelGGL(k_torch_sum_level<0>, dim3(blocks(m.rows / 16 + 1), (unsigned)m.nt), dim3(256), 0, s, m.var, m.B0, (long long)V, m.chunk, 0ll, m.s0);
+    hipLaunchKernelGGL(k_torch_sum_level<1>, dim3(blocks(m.rows / 256 + 1), (unsigned)m.nt), dim3(256), 0, s, m.B0, m.B1, (long long)V, m.chunk, m.s0, m.s1);
+    hipLaunchKernelGGL(k_torch_sum_level<2>, dim3(blocks(m.rows / 4096 + 1), (unsigned)m.nt), dim3(256), 0, s, m.B1, m.B2, (long long)V, m.chunk, m.s1, m.s2);
+    hipLaunchKernelGGL(k_torch_sum_chunks, dim3((unsigned)m.nt), dim3(64), 0, s, m.var, m.B0, m.B1, m.B2, (long long)V, m.chunk, m.s0, m.s1, m.s2, m.slots);
+    hipLaunchKernelGGL(k_torch_sum_final, dim3(1), dim3(1), 0, s, m.slots, m.threads, m.two_pass ? 1 : 0, (long long)V, st);
     return check_last("mind_mean");
 }
 
@@ -854,20 +869,17 @@ int launch_mind_pooled(const float* img, int H, int W, int D, int radius, int di
     if (records) ob = nullptr;
     if (mind_single_pass(img, H, W, D, radius, dilation, ga, gb)) {
         // ONE pass over the image (mindmarch.hip::k_mind_march_pool) + the repair of the blocks where the variance clamp binds; `raw` is not touched
-        Carver cv(workspace, workspace_bytes);
-        float* part = cv.take<float>(2 * 1024);
-        st = cv.take<MindStats>(1);
-        const size_t nblk = (size_t)cdiv(H, ga) * cdiv(W, ga) * cdiv(D, ga);
-        unsigned* blk = cv.take<unsigned>(3 * nblk);
-        if (!cv.ok()) return fail(CVX_ERR_WORKSPACE, "mind_pooled: workspace too small");
+        Carver cv(workspace);
+        const MindWs m = mind_layout(cv, H, W, D, ga, 0);
+        st = m.st;
         const size_t V = (size_t)H * W * D;
         const int nb = (int)(V / 4096 + 1 < 1024 ? V / 4096 + 1 : 1024);
-        hipLaunchKernelGGL(k_minmax_partial, dim3(nb), dim3(256), 0, s, img, V, part);
-        hipLaunchKernelGGL(k_mind_stats_init, dim3(1), dim3(256), 0, s, part, nb, (double)V, st);
-        launch_mind_march_pool(img, H, W, D, ga, oa, gb, records ? rec : static_cast<void*>(ob), records, st, blk, s);
-        const unsigned rgrid = (unsigned)(nblk / 64 + 1 < 1024 ? nblk / 64 + 1 : 1024);
+        hipLaunchKernelGGL(k_minmax_partial, dim3(nb), dim3(256), 0, s, img, V, m.part);
+        hipLaunchKernelGGL(k_mind_stats_init, dim3(1), dim3(256), 0, s, m.part, nb, (double)V, st);
+        launch_mind_march_pool(img, H, W, D, ga, oa, gb, records ? rec : static_cast<void*>(ob), records, st, m.blk, s);
+        const unsigned rgrid = (unsigned)(m.nblk / 64 + 1 < 1024 ? m.nblk / 64 + 1 : 1024);
         const int force = options().mind_single == 2 ? 1 : 0;           // 2: every block through the repair kernel (test of the exact recomputation)
-#define CVX_MR(GA, GB) hipLaunchKernelGGL((k_mind_repair<GA, GB>), dim3(rgrid), dim3(MR_NT), 0, s, img, H, W, D, st, blk, oa, ob, rec, records == 2 ? 1 : 0, mind_exp_table(), force)
+#define CVX_MR(GA, GB) hipLaunchKernelGGL((k_mind_repair<GA, GB>), dim3(rgrid), dim3(MR_NT), 0, s, img, H, W, D, st, m.blk, oa, ob, rec, records == 2 ? 1 : 0, mind_exp_table(), force)
         if (ga == 6 && gb == 2) CVX_MR(6, 2);
         else if (ga == 6 && gb == 3) CVX_MR(6, 3);
         else if (ga == 6 && gb == 6) CVX_MR(6, 6);
@@ -898,11 +910,10 @@ using namespace cvx;
 
 extern "C" size_t cvx_mindssc_workspace_bytes(int H, int W, int D, int radius, int dilation) {
     (void)radius; (void)dilation;
-    size_t n = 256 + 2 * 1024 * sizeof(float) + 256 + sizeof(MindStats) + 256;
-    n += 256 + 3 * sizeof(unsigned) * (size_t)cdiv(H, 2) * cdiv(W, 2) * cdiv(D, 2);             // block statistics of the single-pass pooled path (smallest window: 2)
-    if (options().mind_mean_threads > 0)                                       // var, thread slots, three cascade levels (< V / 14 floats)
-        n += 256 + (size_t)H * W * D * sizeof(float) + 256 + 1024 * sizeof(float) + (size_t)H * W * D / 14 * sizeof(float) + 3 * (256 + 1024 * 64 * sizeof(float));
-    return n;
+    Carver single, two;
+    mind_layout(single, H, W, D, 2, 0);                            // the single pass with the smallest window has the most blocks
+    mind_layout(two, H, W, D, 0, options().mind_mean_threads);
+    return std::max(ws_query(single), ws_query(two));
 }
 
 extern "C" size_t cvx_mindssc_pooled_scratch_bytes(int H, int W, int D, int radius, int dilation, int g1, int g2) {
@@ -934,9 +945,8 @@ extern "C" int cvx_mindssc_pooled_f32(const float* img, int H, int W, int D, int
     if (rc || !repaired_host) return rc;
     *repaired_host = 0;
     if (single) {
-        Carver cv(workspace, workspace_bytes);
-        (void)cv.take<float>(2 * 1024);
-        const MindStats* st = cv.take<MindStats>(1);
+        Carver cv(workspace);
+        const MindStats* st = mind_layout(cv, H, W, D, 0, 0).st;
         unsigned n = 0;
         if (hipMemcpyAsync(&n, &st->n_repair, sizeof(n), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
             return check_last("cvx_mindssc_pooled_f32: repair count");

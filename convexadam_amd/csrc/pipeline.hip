@@ -98,14 +98,8 @@ struct PairLayout {
     size_t V, v, V2;
     // byte offsets into the workspace (0 = not used)
     size_t featF, featM, mind_ws, mind_ws2, fs, ms, corr_ws, corr_ws2, ssd, argmin, mesh, conv_ws, ssd2, argmin2, conv_ws2, cert_ws, cert_ws2, soft, soft2, in1, in2, ic1, ic2, ic_ws,
-        upin, disp_hr, F2, M2, P, m, v_, U, adam_ws, smooth_ws, snaps, bh, bw, bd, bh2, bw2, bd2, total;
+        upin, disp_hr, F2, M2, P, m, v_, U, adam_ws, smooth_ws, smooth_ws2, snaps, bh, bw, bd, bh2, bw2, bd2, total;
 };
-
-static size_t take(size_t& used, size_t bytes) {
-    const size_t off = align_up(used, 256);
-    used = off + bytes;
-    return off;
-}
 
 static PairLayout pair_layout(const cvx_pair_params& p, int n_snap = 0, int max_smooth = 0) {
     PairLayout L{};
@@ -116,56 +110,56 @@ static PairLayout pair_layout(const cvx_pair_params& p, int n_snap = 0, int max_
     const int n = 2 * p.disp_hw + 1;
     L.K = n * n * n;
     L.V = (size_t)p.H * p.W * p.D; L.v = (size_t)L.h * L.w * L.d; L.V2 = (size_t)L.h2 * L.w2 * L.d2;
-    size_t u = 256;      // offset 0 is reserved as "unused"
+    Carver cv; cv.take_bytes(1);    // offset 0 is reserved as "unused"
     const size_t f = sizeof(float);
     if (p.n_feat == 0) {
         // (the pooled path's raw patch SSDs may be blocked by tiles that overhang the volume: mind_pooled_raw_floats >= 12 V)
         const size_t raw_floats = mind_pooled_raw_floats(p.H, p.W, p.D, p.grid_sp, p.lambda_weight > 0 ? p.grid_sp_adam : 0);
-        L.featF = take(u, f * raw_floats);
-        L.featM = take(u, f * raw_floats);
-        L.mind_ws = take(u, cvx_mindssc_workspace_bytes(p.H, p.W, p.D, p.mind_r, p.mind_d));
-        L.mind_ws2 = take(u, cvx_mindssc_workspace_bytes(p.H, p.W, p.D, p.mind_r, p.mind_d));      // the moving image's pass runs beside the fixed one's
+        L.featF = cv.take_bytes(f * raw_floats);
+        L.featM = cv.take_bytes(f * raw_floats);
+        L.mind_ws = cv.take_bytes(cvx_mindssc_workspace_bytes(p.H, p.W, p.D, p.mind_r, p.mind_d));
+        L.mind_ws2 = cv.take_bytes(cvx_mindssc_workspace_bytes(p.H, p.W, p.D, p.mind_r, p.mind_d));      // the moving image's pass runs beside the fixed one's
     }
-    L.fs = take(u, f * L.C * L.v);
-    L.ms = take(u, f * L.C * L.v);
-    L.corr_ws = take(u, cvx_correlate_workspace_bytes(L.C, L.h, L.w, L.d, p.disp_hw));
+    L.fs = cv.take_bytes(f * L.C * L.v);
+    L.ms = cv.take_bytes(f * L.C * L.v);
+    L.corr_ws = cv.take_bytes(cvx_correlate_workspace_bytes(L.C, L.h, L.w, L.d, p.disp_hw));
     // the reverse direction's padded copies (both directions in one launch): only where that path can run (option corr_dual, off by default)
-    L.corr_ws2 = (p.ic && options().corr_dual != 0 && corr_fused_supported(L.C, L.h, L.w, L.d, p.disp_hw)) ? take(u, corr_fused_workspace_bytes(L.C, L.h, L.w, L.d, p.disp_hw)) : 0;
+    L.corr_ws2 = (p.ic && options().corr_dual != 0 && corr_fused_supported(L.C, L.h, L.w, L.d, p.disp_hw)) ? cv.take_bytes(corr_fused_workspace_bytes(L.C, L.h, L.w, L.d, p.disp_hw)) : 0;
     // fp16 storage: the cost volumes hold __half (half the bytes written by the correlation kernel and read by every argmin pass)
     const size_t ssd_elem = p.fp16_storage ? 2 : f;
-    L.ssd = take(u, ssd_elem * (size_t)L.K * L.v);
-    L.argmin = take(u, sizeof(int64_t) * L.v);
-    L.mesh = take(u, f * 3 * (size_t)L.K);
-    L.conv_ws = take(u, cvx_coupled_convex_workspace_bytes(L.h, L.w, L.d, p.disp_hw));
+    L.ssd = cv.take_bytes(ssd_elem * (size_t)L.K * L.v);
+    L.argmin = cv.take_bytes(sizeof(int64_t) * L.v);
+    L.mesh = cv.take_bytes(f * 3 * (size_t)L.K);
+    L.conv_ws = cv.take_bytes(cvx_coupled_convex_workspace_bytes(L.h, L.w, L.d, p.disp_hw));
     // certified decisions on the fast cost volume (certify.hip): one small workspace per direction
-    L.cert_ws = take(u, corr_certify_workspace_bytes(L.C, L.h, L.w, L.d, p.disp_hw));
-    if (p.ic) L.cert_ws2 = take(u, corr_certify_workspace_bytes(L.C, L.h, L.w, L.d, p.disp_hw));
-    L.soft = take(u, f * 3 * L.v);
-    L.bh = take(u, f * L.h); L.bw = take(u, f * L.w); L.bd = take(u, f * L.d);
+    L.cert_ws = cv.take_bytes(corr_certify_workspace_bytes(L.C, L.h, L.w, L.d, p.disp_hw));
+    if (p.ic) L.cert_ws2 = cv.take_bytes(corr_certify_workspace_bytes(L.C, L.h, L.w, L.d, p.disp_hw));
+    L.soft = cv.take_bytes(f * 3 * L.v);
+    L.bh = cv.take_bytes(f * L.h); L.bw = cv.take_bytes(f * L.w); L.bd = cv.take_bytes(f * L.d);
     if (p.ic) {
         // the reverse direction keeps its own cost volume: both coupled-convex solves share their launches
-        L.ssd2 = take(u, ssd_elem * (size_t)L.K * L.v);
-        L.argmin2 = take(u, sizeof(int64_t) * L.v);
-        L.conv_ws2 = take(u, cvx_coupled_convex_workspace_bytes(L.h, L.w, L.d, p.disp_hw));
-        L.soft2 = take(u, f * 3 * L.v);
-        L.in1 = take(u, f * 3 * L.v); L.in2 = take(u, f * 3 * L.v);
-        L.ic1 = take(u, f * 3 * L.v); L.ic2 = take(u, f * 3 * L.v);
-        L.ic_ws = take(u, cvx_inverse_consistency_workspace_bytes(L.h, L.w, L.d));
-        L.upin = take(u, f * 3 * L.v);
-        L.disp_hr = take(u, f * 3 * L.V);
+        L.ssd2 = cv.take_bytes(ssd_elem * (size_t)L.K * L.v);
+        L.argmin2 = cv.take_bytes(sizeof(int64_t) * L.v);
+        L.conv_ws2 = cv.take_bytes(cvx_coupled_convex_workspace_bytes(L.h, L.w, L.d, p.disp_hw));
+        L.soft2 = cv.take_bytes(f * 3 * L.v);
+        L.in1 = cv.take_bytes(f * 3 * L.v); L.in2 = cv.take_bytes(f * 3 * L.v);
+        L.ic1 = cv.take_bytes(f * 3 * L.v); L.ic2 = cv.take_bytes(f * 3 * L.v);
+        L.ic_ws = cv.take_bytes(cvx_inverse_consistency_workspace_bytes(L.h, L.w, L.d));
+        L.upin = cv.take_bytes(f * 3 * L.v);
+        L.disp_hr = cv.take_bytes(f * 3 * L.V);
     }
     if (p.lambda_weight > 0) {
         // planar pooled features, or (MIND path, option mind_records) the Adam loop's records: [CP/4][V2 + 1][4]
-        const size_t f2_bytes = f * (size_t)((L.C + 3) / 4 * 4) * (L.V2 + 1);
-        L.F2 = take(u, f2_bytes);
-        L.M2 = take(u, f2_bytes);
-        L.P = take(u, f * 3 * L.V2); L.m = take(u, f * 3 * L.V2); L.v_ = take(u, f * 3 * L.V2); L.U = take(u, f * 3 * L.V2);
-        L.adam_ws = take(u, cvx_adam_workspace_bytes(L.C, L.h2, L.w2, L.d2));
-        L.bh2 = take(u, f * L.h2); L.bw2 = take(u, f * L.w2); L.bd2 = take(u, f * L.d2);
-        if (p.selected_smooth > 0 || max_smooth > 0) L.smooth_ws = take(u, 2 * (256 + f * 3 * L.V));
-        if (n_snap > 0) L.snaps = take(u, f * 3 * L.V2 * (size_t)n_snap);
+        const size_t f2_bytes = f * adam_record_floats(L.C, L.V2);
+        L.F2 = cv.take_bytes(f2_bytes);
+        L.M2 = cv.take_bytes(f2_bytes);
+        L.P = cv.take_bytes(f * 3 * L.V2); L.m = cv.take_bytes(f * 3 * L.V2); L.v_ = cv.take_bytes(f * 3 * L.V2); L.U = cv.take_bytes(f * 3 * L.V2);
+        L.adam_ws = cv.take_bytes(cvx_adam_workspace_bytes(L.C, L.h2, L.w2, L.d2));
+        L.bh2 = cv.take_bytes(f * L.h2); L.bw2 = cv.take_bytes(f * L.w2); L.bd2 = cv.take_bytes(f * L.d2);
+        if (p.selected_smooth > 0 || max_smooth > 0) { L.smooth_ws = cv.take_bytes(f * 3 * L.V); L.smooth_ws2 = cv.take_bytes(f * 3 * L.V); }
+        if (n_snap > 0) L.snaps = cv.take_bytes(f * 3 * L.V2 * (size_t)n_snap);
     }
-    L.total = u + 256;
+    L.total = ws_query(cv);
     return L;
 }
 
@@ -391,9 +385,10 @@ static int cvx::register_pair_core(const float* img_fixed, const float* img_movi
         if ((rc = cvx_avgpool_f32(featM, L.C, p->H, p->W, p->D, p->grid_sp, F(L.ms), stream))) return rc;
     }
     const size_t vws = cvx_coupled_convex_workspace_bytes(L.h, L.w, L.d, p->disp_hw);
-    // first key buffer of the coupled-convex workspace (carved exactly as coupled_core does): the plain argmin leaves its keys there
-    unsigned long long* keys = Carver(ws + L.conv_ws, vws).take<unsigned long long>(L.v);
-    unsigned long long* keys2 = p->ic ? Carver(ws + L.conv_ws2, vws).take<unsigned long long>(L.v) : nullptr;
+    // the plain argmin leaves its keys in the first key buffer of the coupled-convex workspace
+    Carver cv1(ws + L.conv_ws), cv2(p->ic ? ws + L.conv_ws2 : nullptr);
+    const CoupledWs cw1 = coupled_layout(cv1, L.h, L.w, L.d, p->disp_hw), cw2 = coupled_layout(cv2, L.h, L.w, L.d, p->disp_hw);
+    unsigned long long *keys = cw1.keys[0], *keys2 = cw2.keys[0];
     const bool no_prune = options().no_prune != 0;        // streaming coupled passes need int64 winners
     {
         const bool adam_tables = p->lambda_weight > 0;
@@ -402,8 +397,7 @@ static int cvx::register_pair_core(const float* img_fixed, const float* img_movi
         PairSetup a = {{{L.h, L.w, L.d, L.h2, L.w2, L.d2},
                         {F(L.bh), F(L.bw), F(L.bd), adam_tables ? F(L.bh2) : nullptr, adam_tables ? F(L.bw2) : nullptr, adam_tables ? F(L.bd2) : nullptr}},
                        p->disp_hw, F(L.mesh), {keys, keys2}, L.v,
-                       {no_prune ? nullptr : coupled_ws_counts(ws + L.conv_ws, vws, L.h, L.w, L.d, p->disp_hw),
-                        (no_prune || !p->ic) ? nullptr : coupled_ws_counts(ws + L.conv_ws2, vws, L.h, L.w, L.d, p->disp_hw)},
+                       {no_prune ? nullptr : cw1.counts, no_prune ? nullptr : cw2.counts},
                        {zero_state ? reinterpret_cast<float4*>(ws + L.m) : nullptr, zero_state ? reinterpret_cast<float4*>(ws + L.v_) : nullptr}, 3 * L.V2 / 4};
         hipLaunchKernelGGL(k_pair_setup, dim3(zero_state ? 1024 : 64), dim3(256), 0, s, a);
         if (adam_tables && !zero_state) {
@@ -530,7 +524,7 @@ static int cvx::register_pair_core(const float* img_fixed, const float* img_movi
         // disp_hr = interpolate(fitted_grid * grid_sp_adam, (H,W,D))                            (:182)
         if (n_snap > 0) {                       // self_configuring/convex_adam_MIND.py:115-139: every snapshot x every final smoothing
             float* tmp = F(L.smooth_ws);
-            float* tmp2 = L.smooth_ws ? reinterpret_cast<float*>(ws + align_up(L.smooth_ws + sizeof(float) * 3 * L.V, 256)) : nullptr;
+            float* tmp2 = L.smooth_ws ? F(L.smooth_ws2) : nullptr;
             for (int i = 0; i < n_snap; ++i)
                 for (int j = 0; j < n_smooth; ++j) {
                     float* dst = out_field + ((size_t)i * n_smooth + j) * 3 * L.V;
@@ -545,7 +539,7 @@ static int cvx::register_pair_core(const float* img_fixed, const float* img_movi
                 }
         } else if (p->selected_smooth > 0) {
             float* tmp = F(L.smooth_ws);
-            float* tmp2 = reinterpret_cast<float*>(ws + align_up(L.smooth_ws + sizeof(float) * 3 * L.V, 256));
+            float* tmp2 = F(L.smooth_ws2);
             if ((rc = launch_resize(F(L.U), 3, L.h2, L.w2, L.d2, tmp, p->H, p->W, p->D, (float)p->grid_sp_adam, 1.0f, s))) return rc;
             if ((rc = launch_box_zero(tmp, tmp2, 3, p->H, p->W, p->D, p->selected_smooth, false, s))) return rc;
             if ((rc = launch_box_zero(tmp2, tmp, 3, p->H, p->W, p->D, p->selected_smooth, false, s))) return rc;

@@ -650,7 +650,9 @@ static int check_smoother(const cvx_smoother* sm) {
     }
     return CVX_OK;
 }
-extern "C" size_t cvx_smooth_workspace_bytes(int C, int H, int W, int D) { return 256 + sizeof(float) * (size_t)C * H * W * D; }
+// the smoothers' workspace: one temporary volume (box smoothing: for two passes or more)
+static float* smooth_layout(Carver& cv, int C, int H, int W, int D, bool tmp) { return tmp ? cv.take<float>((size_t)C * H * W * D) : nullptr; }
+extern "C" size_t cvx_smooth_workspace_bytes(int C, int H, int W, int D) { Carver m; smooth_layout(m, C, H, W, D, true); return ws_query(m); }
 extern "C" int cvx_smooth_f32(const float* in, int C, int H, int W, int D, const cvx_smoother* sm, int backward, float* out,
                               void* workspace, size_t workspace_bytes, void* stream) {
     CVX_REQUIRE(in && out && in != out && workspace, "cvx_smooth_f32: bad pointers");
@@ -658,8 +660,8 @@ extern "C" int cvx_smooth_f32(const float* in, int C, int H, int W, int D, const
     int rc = check_smoother(sm);
     if (rc) return rc;
     if (workspace_bytes < cvx_smooth_workspace_bytes(C, H, W, D)) return fail(CVX_ERR_WORKSPACE, "cvx_smooth_f32: workspace too small");
-    Carver cv(workspace, workspace_bytes);
-    float* tmp = cv.take<float>((size_t)C * H * W * D);
+    Carver cv(workspace);
+    float* tmp = smooth_layout(cv, C, H, W, D, true);
     return launch_smoother(in, out, tmp, C, H, W, D, *sm, backward != 0, as_stream(stream));
 }
 
@@ -680,9 +682,7 @@ extern "C" int cvx_select_f32(const float* mask, const float* a, const float* b,
     return check_last("select");
 }
 
-extern "C" size_t cvx_box_smooth_workspace_bytes(int C, int H, int W, int D, int passes) {
-    return passes > 1 ? 256 + sizeof(float) * (size_t)C * H * W * D : 0;
-}
+extern "C" size_t cvx_box_smooth_workspace_bytes(int C, int H, int W, int D, int passes) { Carver m; smooth_layout(m, C, H, W, D, passes > 1); return ws_query(m); }
 extern "C" int cvx_box_smooth_f32(const float* in, int C, int H, int W, int D, int k, int passes, float* out,
                                   void* workspace, size_t workspace_bytes, void* stream) {
     CVX_REQUIRE(in && out, "cvx_box_smooth_f32: null pointer");
@@ -694,8 +694,8 @@ extern "C" int cvx_box_smooth_f32(const float* in, int C, int H, int W, int D, i
         return fail(CVX_ERR_WORKSPACE, "cvx_box_smooth_f32: workspace too small");
     CVX_REQUIRE(in != out, "cvx_box_smooth_f32: in-place not supported");
     hipStream_t s = as_stream(stream);
-    Carver cv(workspace, workspace_bytes);
-    float* tmp = passes > 1 ? cv.take<float>((size_t)C * H * W * D) : nullptr;
+    Carver cv(workspace);
+    float* tmp = smooth_layout(cv, C, H, W, D, passes > 1);
     // ping-pong so that the last pass lands in `out`
     const float* src = in;
     for (int p = 0; p < passes; ++p) {

@@ -314,14 +314,17 @@ __global__ __launch_bounds__(256) void k_affine_warp(const float* __restrict__ v
 
 using namespace cvx;
 
+// residual bits, inlier selection, the status word
+struct LtsWs { unsigned* rbits; unsigned char* sel; int* status; };
+static LtsWs lts_layout(Carver& cv, int64_t n) { return LtsWs{cv.take<unsigned>((size_t)n), cv.take<unsigned char>((size_t)n), cv.take<int>(1)}; }
 extern "C" size_t cvx_rigid_lts_workspace_bytes(int64_t n) {
     if (n < 2 || n > LTS_MAX_N) return 0;
-    return align_up((size_t)n * sizeof(unsigned), 256) + align_up((size_t)n, 256) + 256;
+    Carver m; lts_layout(m, n); return align_up(m.used, 256);          // (no slack: the status word rounded to its granule, as this query always was)
 }
 
 extern "C" int cvx_rigid_lts_f32(const float* fixed, int ld_fixed, const float* moving, int ld_moving, int64_t n, int iters, float* T,
-                                 unsigned char* inliers, void* ws, size_t ws_bytes, void* stream) {
-    CVX_REQUIRE(fixed && moving && T && ws, "cvx_rigid_lts_f32: null pointer");
+                                 unsigned char* inliers, void* workspace, size_t workspace_bytes, void* stream) {
+    CVX_REQUIRE(fixed && moving && T && workspace, "cvx_rigid_lts_f32: null pointer");
     CVX_REQUIRE(n >= 2 && n <= LTS_MAX_N, "cvx_rigid_lts_f32: n = %lld outside 2..%lld", (long long)n, (long long)LTS_MAX_N);
     CVX_REQUIRE(iters >= 1, "cvx_rigid_lts_f32: iters = %d < 1", iters);
     if (iters == 1)
@@ -329,11 +332,9 @@ extern "C" int cvx_rigid_lts_f32(const float* fixed, int ld_fixed, const float* 
     else
         CVX_REQUIRE(ld_fixed == 4 && ld_moving == 4, "cvx_rigid_lts_f32: the trimmed fit needs (n, 4) points (ld %d, %d)", ld_fixed, ld_moving);
     const size_t need = cvx_rigid_lts_workspace_bytes(n);
-    if (ws_bytes < need) return fail(CVX_ERR_WORKSPACE, "cvx_rigid_lts_f32: workspace %zu < %zu bytes", ws_bytes, need);
-    Carver cv(ws, ws_bytes);
-    unsigned* rbits = cv.take<unsigned>((size_t)n);
-    unsigned char* sel = cv.take<unsigned char>((size_t)n);
-    int* status = cv.take<int>(1);
+    if (workspace_bytes < need) return fail(CVX_ERR_WORKSPACE, "cvx_rigid_lts_f32: workspace %zu < %zu bytes", workspace_bytes, need);
+    Carver cv(workspace);
+    const auto [rbits, sel, status] = lts_layout(cv, n);
     hipStream_t s = as_stream(stream);
     hipLaunchKernelGGL(k_rigid_lts, dim3(1), dim3(LTS_THREADS), 0, s, fixed, ld_fixed, moving, ld_moving, (int)n, iters, T, inliers, rbits, sel, status);
     int rc = check_last("rigid_lts");

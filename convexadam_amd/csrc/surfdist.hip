@@ -710,13 +710,26 @@ static size_t surf_vox_cap(int H, int W, int D) {
     const size_t vox = (size_t)H * W * D + 64;
     return vox < ((size_t)1 << 14) ? vox : ((size_t)1 << 14);
 }
-// bits_b / bits_a = cvx_label_bits_u64 of the two maps; otherwise as cvx_surface_distance_hist_i64 (same counts, same flags)
+// counters, then the word and voxel lists (capacities per sub-list; beyond them the call reports flag 2)
+static SurfLists surf_layout(Carver& cv, int H, int W, int D, int num_labels) {
+    SurfLists L;
+    unsigned* counters = cv.take<unsigned>(5 * SURF_NL);
+    auto at = [counters](int i) { return counters ? counters + i * SURF_NL : nullptr; };      // (a measuring carver hands out null)
+    L.cap_words = (unsigned)surf_list_cap(H, W, D, num_labels);
+    L.cap_far = (unsigned)surf_vox_cap(H, W, D);
+    L.cap_vox = L.cap_far;
+    for (int i = 0; i < 2; ++i) { L.words[i] = cv.take<SurfWord>((size_t)L.cap_words * SURF_NL); L.n_words[i] = at(i); }
+    for (int i = 0; i < 2; ++i) { L.vox[i] = cv.take<unsigned long long>((size_t)L.cap_vox * SURF_NL); L.n_vox[i] = at(2 + i); }
+    L.far = cv.take<unsigned long long>((size_t)L.cap_far * SURF_NL);
+    L.n_far = at(4);
+    return L;
+}
 extern "C" size_t cvx_surface_distance_hist_bits_workspace_bytes(int H, int W, int D, int num_labels) {
     if (H <= 0 || W <= 0 || D <= 0 || num_labels <= 0) return 0;
-    const size_t cap_words = surf_list_cap(H, W, D, num_labels), cap_far = surf_vox_cap(H, W, D);       // per sub-list; beyond that the call reports flag 2
-    return 256 + sizeof(unsigned) * 5 * SURF_NL + 2 * (256 + sizeof(SurfWord) * cap_words * SURF_NL) + 3 * (256 + sizeof(unsigned long long) * cap_far * SURF_NL) + 256;
+    Carver m; surf_layout(m, H, W, D, num_labels); return ws_query(m);
 }
 
+// bits_b / bits_a = cvx_label_bits_u64 of the two maps; otherwise as cvx_surface_distance_hist_i64 (same counts, same flags)
 extern "C" int cvx_surface_distance_hist_bits_i64(const uint64_t* bits_b, const uint64_t* bits_a, int H, int W, int D, int num_labels,
                                                   const uint64_t* active4, int nbins, int64_t* hist, int64_t hist_stride, int* overflow,
                                                   int overflow_stride, int max_radius, void* workspace, size_t workspace_bytes, void* stream) {
@@ -732,16 +745,9 @@ extern "C" int cvx_surface_distance_hist_bits_i64(const uint64_t* bits_b, const 
     const size_t words = (size_t)num_labels * H * W * nseg;
     CVX_REQUIRE((int64_t)H * W * nseg <= INT_MAX - 65536 && words < ((size_t)1 << 32), "cvx_surface_distance_hist_bits_i64: volume too large");
     hipStream_t s = as_stream(stream);
-    Carver cv(workspace, workspace_bytes);
-    unsigned* counters = cv.take<unsigned>(5 * SURF_NL);
-    SurfLists L;
-    L.cap_words = (unsigned)surf_list_cap(H, W, D, num_labels);
-    L.cap_far = (unsigned)surf_vox_cap(H, W, D);
-    L.cap_vox = L.cap_far;
-    for (int i = 0; i < 2; ++i) { L.words[i] = cv.take<SurfWord>((size_t)L.cap_words * SURF_NL); L.n_words[i] = counters + i * SURF_NL; }
-    for (int i = 0; i < 2; ++i) { L.vox[i] = cv.take<unsigned long long>((size_t)L.cap_vox * SURF_NL); L.n_vox[i] = counters + (2 + i) * SURF_NL; }
-    L.far = cv.take<unsigned long long>((size_t)L.cap_far * SURF_NL);
-    L.n_far = counters + 4 * SURF_NL;
+    Carver cv(workspace);
+    const SurfLists L = surf_layout(cv, H, W, D, num_labels);
+    unsigned* counters = L.n_words[0];
     if (hipMemsetAsync(counters, 0, 5 * SURF_NL * sizeof(unsigned), s) != hipSuccess) return fail(CVX_ERR_LAUNCH, "surface_distance_hist_bits: memset failed");
     const unsigned long long* Bb = reinterpret_cast<const unsigned long long*>(bits_b);
     const unsigned long long* Ba = reinterpret_cast<const unsigned long long*>(bits_a);

@@ -389,10 +389,19 @@ __global__ __launch_bounds__(256) void k_resize_ac(const float* __restrict__ in,
 
 using namespace cvx;
 
+// the augmented system [N][lda], its pivots, the status word
+struct TpsWs { float* A; int *piv, *info; };
+static TpsWs tps_layout(Carver& cv, int n, int nrhs) {
+    const size_t N = (size_t)n + 4;
+    TpsWs t;
+    t.A = cv.take<float>(N * (size_t)tps_lda(n, nrhs));
+    t.piv = cv.take<int>(N);
+    t.info = cv.take<int>(1);
+    return t;
+}
 extern "C" size_t cvx_tps_fit_workspace_bytes(int n, int nrhs) {
     if (n < 1 || n > TPS_MAX_N || nrhs < 1 || nrhs > TPS_MAX_RHS) return 0;
-    const size_t N = (size_t)n + 4;
-    return align_up(N * (size_t)tps_lda(n, nrhs) * sizeof(float), 256) + align_up(N * sizeof(int), 256) + 256;
+    Carver m; tps_layout(m, n, nrhs); return align_up(m.used, 256);    // (no slack: the status word rounded to its granule, as this query always was)
 }
 
 extern "C" int cvx_tps_fit_f32(const float* centres, const float* values, int n, int nrhs, float lambd, float* theta, void* workspace,
@@ -404,9 +413,8 @@ extern "C" int cvx_tps_fit_f32(const float* centres, const float* values, int n,
     const size_t need = cvx_tps_fit_workspace_bytes(n, nrhs);
     if (workspace_bytes < need) return fail(CVX_ERR_WORKSPACE, "cvx_tps_fit_f32: workspace %zu < %zu bytes", workspace_bytes, need);
     const int N = n + 4, ncol = N + nrhs, lda = tps_lda(n, nrhs);
-    float* A = static_cast<float*>(workspace);
-    int* piv = reinterpret_cast<int*>(static_cast<char*>(workspace) + align_up((size_t)N * lda * sizeof(float), 256));
-    int* info = reinterpret_cast<int*>(reinterpret_cast<char*>(piv) + align_up((size_t)N * sizeof(int), 256));
+    Carver cv(workspace);
+    const auto [A, piv, info] = tps_layout(cv, n, nrhs);
     hipStream_t s = as_stream(stream);
     if (hipMemsetAsync(info, 0, sizeof(int), s) != hipSuccess) { (void)hipGetLastError(); return fail(CVX_ERR_LAUNCH, "cvx_tps_fit_f32: memset failed"); }
     hipLaunchKernelGGL(k_tps_assemble, dim3((unsigned)cdiv(ncol, 256), (unsigned)N), dim3(256), 0, s, centres, values, n, nrhs, lambd, A, lda, info);
