@@ -42,6 +42,12 @@ class PairParams(C.Structure):
                 ("fp16_storage", C.c_int), ("ctx", C.c_void_p), ("adam_fast", C.c_int), ("reserved_", C.c_int * 3)]
 
 
+class StageParams(C.Structure):
+    """struct cvx_convex_stage_params (include/convexadam_hip.h)."""
+    _fields_ = [("C", C.c_int), ("h", C.c_int), ("w", C.c_int), ("d", C.c_int), ("disp_hw", C.c_int), ("grid_sp", C.c_int),
+                ("ic_iters", C.c_int), ("H", C.c_int), ("W", C.c_int), ("D", C.c_int), ("ctx", C.c_void_p), ("reserved_", C.c_int * 4)]
+
+
 _vp, _i, _f, _sz, _i64 = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_int64
 
 # name -> (restype, argtypes); this table is also what tests/test_abi.py checks against the header
@@ -87,6 +93,7 @@ SIGNATURES = {
     "cvx_correlate_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "cvx_coupled_convex_workspace_bytes": (_sz, [_i] * 4),
     "cvx_coupled_convex_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "cvx_coupled_convex_masked_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "cvx_coupled_convex_f16": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "cvx_inverse_consistency_workspace_bytes": (_sz, [_i] * 3),
     "cvx_inverse_consistency_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
@@ -148,6 +155,12 @@ SIGNATURES = {
     "cvx_rigid_lts_workspace_bytes": (_sz, [_i64]),
     "cvx_rigid_lts_f32": (_i, [_vp, _i, _vp, _i, _i64, _i, _vp, _vp, _vp, _sz, _vp]),
     "cvx_affine_warp_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "cvx_threshold_pool_mask_u8": (_i, [_vp, _i, _i, _i, _f, _i, _vp, _vp]),
+    "cvx_label_centroids_i64": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    "cvx_rigid_samples_workspace_bytes": (_sz, [_i] * 6),
+    "cvx_rigid_samples_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "cvx_convex_stage_workspace_bytes": (_sz, [C.POINTER(StageParams)]),
+    "cvx_convex_stage_f32": (_i, [_vp, _vp, _vp, _vp, C.POINTER(StageParams), _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

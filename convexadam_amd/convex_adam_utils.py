@@ -138,11 +138,22 @@ def correlate(mind_fix, mind_mov, disp_hw, grid_sp, shape, ch=12, cost="ssd", n_
     return ssd, am
 
 
-def coupled_convex(ssd, ssd_argmin, disp_mesh_t, grid_sp, shape):
-    """Coupled convex regularisation -> (1,3,H',W',D') in coarse-voxel units.  (convex_adam_utils.py:93-109)"""
-    ssd = require_device_tensor(ssd, "ssd")
+def coupled_convex(ssd, ssd_argmin, disp_mesh_t, grid_sp, shape, cell_mask=None):
+    """Coupled convex regularisation -> (1,3,H',W',D') in coarse-voxel units.  (convex_adam_utils.py:93-109)
+    cell_mask (H',W',D') (optionally with leading 1s; non-zero = keep): the result on ssd * cell_mask, the cost-volume masking of
+    l2r_2020_convexAdam_CuRIOUS.py:336-338, without writing `ssd` (float32 volumes only).  `ssd_argmin` stays the argmin of the unmasked
+    volume, as in the script.  Columns of masked-out cells are not read: a NaN there does not reach the result."""
     H, W, D = int(shape[0]), int(shape[1]), int(shape[2])
     h, w, d = H // grid_sp, W // grid_sp, D // grid_sp
+    if cell_mask is not None:                               # metadata only: a bad mask is a ValueError for CPU tensors too
+        if not isinstance(cell_mask, torch.Tensor):
+            raise TypeError("cell_mask must be a torch.Tensor")
+        ms = tuple(int(s) for s in cell_mask.shape)
+        if len(ms) < 3 or ms[-3:] != (h, w, d) or any(s != 1 for s in ms[:-3]):
+            raise ValueError("coupled_convex: cell_mask must be (%d, %d, %d) (optionally with leading 1s), got %s" % (h, w, d, ms))
+        if isinstance(ssd, torch.Tensor) and ssd.dtype == torch.float16:
+            raise ValueError("coupled_convex: cell_mask needs a float32 cost volume (fp16 storage of the masked path is not built)")
+    ssd = require_device_tensor(ssd, "ssd")
     K = int(ssd.shape[0])
     n = int(round(K ** (1.0 / 3.0)))
     if n ** 3 != K or tuple(ssd.shape[1:]) != (h, w, d):
@@ -155,8 +166,13 @@ def coupled_convex(ssd, ssd_argmin, disp_mesh_t, grid_sp, shape):
     nws = lib().cvx_coupled_convex_workspace_bytes(h, w, d, (n - 1) // 2)
     ws = workspace(nws, s.device)
     with torch.cuda.device(s.device):
-        fn = lib().cvx_coupled_convex_f16 if half else lib().cvx_coupled_convex_f32
-        check(fn(ptr(s), ptr(am), ptr(mesh), h, w, d, (n - 1) // 2, ptr(out), ptr(ws), nws, stream_ptr(s.device)))
+        if cell_mask is not None:
+            cm = (cell_mask.to(s.device) != 0).to(torch.uint8).reshape(h, w, d).contiguous()
+            check(lib().cvx_coupled_convex_masked_f32(ptr(s), ptr(am), ptr(mesh), ptr(cm), h, w, d, (n - 1) // 2, ptr(out), ptr(ws), nws,
+                                                      stream_ptr(s.device)))
+        else:
+            fn = lib().cvx_coupled_convex_f16 if half else lib().cvx_coupled_convex_f32
+            check(fn(ptr(s), ptr(am), ptr(mesh), h, w, d, (n - 1) // 2, ptr(out), ptr(ws), nws, stream_ptr(s.device)))
     return out if disp_mesh_t.dtype == torch.float32 else out.to(disp_mesh_t.dtype)
 
 
@@ -458,3 +474,5 @@ def gpu_usage():
 from .tps import TPS, thin_plate_dense, tps_densify  # noqa: E402,F401
 # least-trimmed rigid fit and fused affine warp (convex_adam_utils.py:173-193, l2r_2020_convexAdam_CuRIOUS.py:349-390): csrc/rigid.hip
 from .rigid import affine_warp, find_rigid_3d, least_trimmed_rigid, rigid_from_field  # noqa: E402,F401
+# the script's coarse foreground mask and landmark score (l2r_2020_convexAdam_CuRIOUS.py:312-319,328-330): csrc/rigidreg.hip
+from .rigid import convex_adam_rigid, convex_stage, label_centroids, landmark_tre, rigid_samples, threshold_pool_mask  # noqa: E402,F401

@@ -35,13 +35,21 @@ template <> struct SsdIO<__half> {
     }
 };
 
+// Cell mask of the cost volume (cvx_coupled_convex_masked_f32; nullptr = every cell kept): the passes see ssd * cell_mask[None] -- the
+// column of a masked-out cell as K zeros -- without that product ever being stored.  A kept entry times 1 is the entry itself (NaN and
+// -0 included); a masked-out entry is never loaded.
+__device__ __forceinline__ bool cell_kept(const unsigned char* __restrict__ cmask, size_t x) { return !cmask || cmask[x] != 0; }
+template <typename ST>
+__device__ __forceinline__ float ld_kept(const ST* p, bool keep) { return keep ? SsdIO<ST>::ld(p) : 0.0f; }
+
 template <bool COUPLED, typename ST>
 __global__ __launch_bounds__(256) void k_argmin(const ST* __restrict__ ssd, const float* __restrict__ mesh,
                                                 const float* __restrict__ u, float coef, int K, size_t v, int kslice,
-                                                unsigned long long* __restrict__ keys) {
+                                                unsigned long long* __restrict__ keys, const unsigned char* __restrict__ cmask) {
     const size_t x = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int k0 = blockIdx.y * kslice, k1 = min(k0 + kslice, K);
     if (x >= v) return;
+    const bool keep = cell_kept(cmask, x);
     float u0 = 0.f, u1 = 0.f, u2 = 0.f;
     if (COUPLED) { u0 = u[x]; u1 = u[v + x]; u2 = u[2 * v + x]; }
     float best = 0.f;
@@ -49,7 +57,7 @@ __global__ __launch_bounds__(256) void k_argmin(const ST* __restrict__ ssd, cons
     const ST* p = ssd + (size_t)k0 * v + x;
 #pragma unroll 4
     for (int k = k0; k < k1; ++k, p += v) {
-        float cost = SsdIO<ST>::ld(p);
+        float cost = ld_kept(p, keep);
         if (COUPLED) {
             const float e0 = mesh[k] - u0, e1 = mesh[K + k] - u1, e2 = mesh[2 * K + k] - u2;
             float q = e0 * e0;          // (..).pow(2).sum(0): sequential over the 3 components
@@ -67,10 +75,12 @@ __global__ __launch_bounds__(256) void k_argmin(const ST* __restrict__ ssd, cons
 template <bool COUPLED, typename ST>
 __global__ __launch_bounds__(256) void k_argmin4(const ST* __restrict__ ssd, const float* __restrict__ mesh,
                                                  const float* __restrict__ u, float coef, int K, size_t v, int kslice,
-                                                 unsigned long long* __restrict__ keys) {
+                                                 unsigned long long* __restrict__ keys, const unsigned char* __restrict__ cmask) {
     const size_t x = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
     const int k0 = blockIdx.y * kslice, k1 = min(k0 + kslice, K);
     if (x >= v) return;
+    const bool keep[4] = {cell_kept(cmask, x), cell_kept(cmask, x + 1), cell_kept(cmask, x + 2), cell_kept(cmask, x + 3)};
+    const bool any_kept = keep[0] | keep[1] | keep[2] | keep[3];
     float u0[4] = {0.f, 0.f, 0.f, 0.f}, u1[4] = {0.f, 0.f, 0.f, 0.f}, u2[4] = {0.f, 0.f, 0.f, 0.f};
     if (COUPLED) {
         const float4 a = *reinterpret_cast<const float4*>(u + x), b = *reinterpret_cast<const float4*>(u + v + x),
@@ -84,8 +94,8 @@ __global__ __launch_bounds__(256) void k_argmin4(const ST* __restrict__ ssd, con
     const ST* p = ssd + (size_t)k0 * v + x;
 #pragma unroll 4
     for (int k = k0; k < k1; ++k, p += v) {
-        const float4 q4 = SsdIO<ST>::ld4(p);
-        const float cst[4] = {q4.x, q4.y, q4.z, q4.w};
+        const float4 q4 = any_kept ? SsdIO<ST>::ld4(p) : make_float4(0.f, 0.f, 0.f, 0.f);
+        const float cst[4] = {keep[0] ? q4.x : 0.f, keep[1] ? q4.y : 0.f, keep[2] ? q4.z : 0.f, keep[3] ? q4.w : 0.f};
         float m0 = 0.f, m1 = 0.f, m2 = 0.f;
         if (COUPLED) { m0 = mesh[k]; m1 = mesh[K + k]; m2 = mesh[2 * K + k]; }
 #pragma unroll
@@ -178,7 +188,8 @@ struct CandBox {
 // would otherwise go to the list; both kernels evaluate the same function, so they see the same box.
 template <typename ST>
 __device__ __forceinline__ CandBox cand_box(const float* __restrict__ mesh, float uc, float ub, float ua, float coef, int K, int n,
-                                            int kp, float ssd_kp, float sm_x, const ST* __restrict__ col, size_t v, int refine_above) {
+                                            int kp, float ssd_kp, float sm_x, const ST* __restrict__ col, size_t v, int refine_above,
+                                            bool keep) {
     CandBox c;
     c.uc = uc; c.ub = ub; c.ua = ua; c.sm = sm_x;
     c.kp = kp;
@@ -205,7 +216,7 @@ __device__ __forceinline__ CandBox cand_box(const float* __restrict__ mesh, floa
             float qn = f0 * f0;
             qn += f1 * f1;
             qn += f2 * f2;
-            const float near_cost = SsdIO<ST>::ld(col + (size_t)kn * v) + coef * qn;          // the reference cost of the nearest displacement
+            const float near_cost = ld_kept(col + (size_t)kn * v, keep) + coef * qn;         // the reference cost of the nearest displacement
             if (near_cost < c.bound) { c.bound = near_cost; c.kp = kn; close_box(); }
         }
     }
@@ -229,7 +240,8 @@ __global__ __launch_bounds__(64) void k_argmin_voxel(const ST* __restrict__ ssd,
                                                      const float* __restrict__ smin, const PrevT* __restrict__ kprev, int limit,
                                                      unsigned long long* __restrict__ list, int* __restrict__ list_count,
                                                      int* __restrict__ next_count, unsigned long long* __restrict__ keys,
-                                                     const unsigned long long* __restrict__ minkeys, int refine, Prob2 o) {
+                                                     const unsigned long long* __restrict__ minkeys, int refine, Prob2 o,
+                                                     const unsigned char* __restrict__ cmask) {
     if (blockIdx.y) {
         ssd = shifted(ssd, o.ssd); u = shifted(u, o.out); smin = shifted(smin, o.ws); kprev = shifted(kprev, o.ws);
         list = shifted(list, o.ws); list_count = shifted(list_count, o.ws); next_count = shifted(next_count, o.ws);
@@ -242,7 +254,8 @@ __global__ __launch_bounds__(64) void k_argmin_voxel(const ST* __restrict__ ssd,
     if (x >= v) return;
     // the voxel's own previous winner, its cost and the per-voxel minimum do not depend on the smoothing: loads issued first
     const int kp = (int)(unsigned)kprev[x];                 // low 32 bits of a key = displacement index
-    const float ssd_kp = SsdIO<ST>::ld(ssd + (size_t)kp * v + x);
+    const bool keep = cell_kept(cmask, x);
+    const float ssd_kp = ld_kept(ssd + (size_t)kp * v + x, keep);
     const float sm_x = smin[x];
     float uc, ub, ua;
     smooth_winner(kprev, mesh, K, h, w, d, x, uc, ub, ua);
@@ -251,7 +264,7 @@ __global__ __launch_bounds__(64) void k_argmin_voxel(const ST* __restrict__ ssd,
     // argmin's winner, and stays it.  minkeys = the (cost, index) keys of the library's own minimum pass: on the public entry points the
     // caller's `argmin` only seeds the first smoothing step and need not be the first NaN
     if (sm_x != sm_x) { keys[x] = pack_min_key(sm_x, minkeys ? (unsigned)(minkeys[x] & 0xffffffffull) : (unsigned)kp); return; }
-    const CandBox c = cand_box(mesh, uc, ub, ua, coef, K, n, kp, ssd_kp, sm_x, ssd + x, v, refine);
+    const CandBox c = cand_box(mesh, uc, ub, ua, coef, K, n, kp, ssd_kp, sm_x, ssd + x, v, refine, keep);
     if (c.vol > min(limit, 8)) {        // (8 = NB below) hand the box over in chunks of 256 displacements: (voxel << 8 | chunk) work items
         const int nchunks = (int)((c.vol + 255) >> 8);
         const int at = atomicAdd(list_count, nchunks);
@@ -285,7 +298,7 @@ __global__ __launch_bounds__(64) void k_argmin_voxel(const ST* __restrict__ ssd,
         }
     }
 #pragma unroll
-    for (int j = 0; j < NB; ++j) val[j] = need[j] ? SsdIO<ST>::ld(ssd + (size_t)kk[j] * v + x) : 0.0f;
+    for (int j = 0; j < NB; ++j) val[j] = ld_kept(ssd + (size_t)kk[j] * v + x, need[j] && keep);
     float best = 0.0f;
     int bi = -1;
 #pragma unroll
@@ -299,14 +312,15 @@ __global__ __launch_bounds__(64) void k_argmin_voxel(const ST* __restrict__ ssd,
 
 template <typename ST>
 __device__ void argmin4_stream(const ST* __restrict__ ssd, const float* __restrict__ mesh, const float* __restrict__ u, float coef, int K,
-                               size_t v, unsigned long long* __restrict__ keys, bool vec);
+                               size_t v, unsigned long long* __restrict__ keys, bool vec, const unsigned char* __restrict__ cmask);
 
 template <typename PrevT, typename ST>
 __global__ __launch_bounds__(256) void k_argmin_wave(const ST* __restrict__ ssd, const float* __restrict__ mesh,
                                                      const float* __restrict__ u, float coef, int K, int n, size_t v,
                                                      const float* __restrict__ smin, const PrevT* __restrict__ kprev,
                                                      const unsigned long long* __restrict__ list, const int* __restrict__ list_count,
-                                                     unsigned long long* __restrict__ keys, int stream_above, int vec, int refine, Prob2 o) {
+                                                     unsigned long long* __restrict__ keys, int stream_above, int vec, int refine, Prob2 o,
+                                                     const unsigned char* __restrict__ cmask) {
     if (blockIdx.y) {
         ssd = shifted(ssd, o.ssd); u = shifted(u, o.out); smin = shifted(smin, o.ws); kprev = shifted(kprev, o.ws);
         list = shifted(list, o.ws); list_count = shifted(list_count, o.ws); keys = shifted(keys, o.ws);
@@ -314,13 +328,14 @@ __global__ __launch_bounds__(256) void k_argmin_wave(const ST* __restrict__ ssd,
     const int lane = threadIdx.x & 63;
     const int wave = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6), nwaves = (int)((gridDim.x * blockDim.x) >> 6);
     const int cnt = *list_count;
-    if (cnt > stream_above) { argmin4_stream(ssd, mesh, u, coef, K, v, keys, vec != 0); return; }   // too many large boxes: one coalesced scan
+    if (cnt > stream_above) { argmin4_stream(ssd, mesh, u, coef, K, v, keys, vec != 0, cmask); return; }   // too many large boxes: one coalesced scan
     for (int e = wave; e < cnt; e += nwaves) {
         const unsigned long long item = list[e];
         const size_t x = (size_t)(item >> 8);
         const long long first = (long long)(item & 255) << 8;              // 256 displacements of the box: 4 per lane
         const int kp = (int)(unsigned)kprev[x];
-        const CandBox c = cand_box(mesh, u[x], u[v + x], u[2 * v + x], coef, K, n, kp, SsdIO<ST>::ld(ssd + (size_t)kp * v + x), smin[x], ssd + x, v, refine);
+        const bool keep = cell_kept(cmask, x);
+        const CandBox c = cand_box(mesh, u[x], u[v + x], u[2 * v + x], coef, K, n, kp, ld_kept(ssd + (size_t)kp * v + x, keep), smin[x], ssd + x, v, refine, keep);
         const int nc = c.c_hi - c.c_lo + 1, nb = c.b_hi - c.b_lo + 1;
         int kk[4];
         float pen[4];
@@ -341,7 +356,7 @@ __global__ __launch_bounds__(256) void k_argmin_wave(const ST* __restrict__ ssd,
         }
         float val[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) val[j] = need[j] ? SsdIO<ST>::ld(ssd + (size_t)kk[j] * v + x) : 0.0f;
+        for (int j = 0; j < 4; ++j) val[j] = ld_kept(ssd + (size_t)kk[j] * v + x, need[j] && keep);
         unsigned long long key = ~0ull;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -362,7 +377,7 @@ __global__ __launch_bounds__(256) void k_argmin_wave(const ST* __restrict__ ssd,
 // same winner again through atomicMin.
 template <typename ST>
 __device__ void argmin4_stream(const ST* __restrict__ ssd, const float* __restrict__ mesh, const float* __restrict__ u, float coef, int K,
-                               size_t v, unsigned long long* __restrict__ keys, bool vec) {
+                               size_t v, unsigned long long* __restrict__ keys, bool vec, const unsigned char* __restrict__ cmask) {
     const int xb = (int)((((v + 3) >> 2) + 255) >> 8);                   // blocks of 256 threads x 4 voxels
     int nslices = (int)gridDim.x * 2 / xb;                                // about two tiles per workgroup
     nslices = nslices < 1 ? 1 : (nslices > K ? K : nslices);
@@ -376,13 +391,21 @@ __device__ void argmin4_stream(const ST* __restrict__ ssd, const float* __restri
         const int nv = (int)min((size_t)4, v - x0);
         float u0[4], u1[4], u2[4], best[4] = {0.f, 0.f, 0.f, 0.f};
         int bi[4] = {-1, -1, -1, -1};
-        for (int j = 0; j < 4; ++j) { const size_t x = x0 + (j < nv ? j : 0); u0[j] = u[x]; u1[j] = u[v + x]; u2[j] = u[2 * v + x]; }
+        bool keep[4], any_kept = false;
+        for (int j = 0; j < 4; ++j) {
+            const size_t x = x0 + (j < nv ? j : 0);
+            u0[j] = u[x]; u1[j] = u[v + x]; u2[j] = u[2 * v + x];
+            keep[j] = j < nv && cell_kept(cmask, x);
+            any_kept |= keep[j];
+        }
         for (int k = k0; k < k1; ++k) {
             const float m0 = mesh[k], m1 = mesh[K + k], m2 = mesh[2 * K + k];
             const ST* p = ssd + (size_t)k * v + x0;
             float c4[4];
-            if (vec) { const float4 q4 = SsdIO<ST>::ld4(p); c4[0] = q4.x; c4[1] = q4.y; c4[2] = q4.z; c4[3] = q4.w; }
-            else for (int j = 0; j < 4; ++j) c4[j] = j < nv ? SsdIO<ST>::ld(p + j) : 0.0f;
+            if (vec) {
+                const float4 q4 = any_kept ? SsdIO<ST>::ld4(p) : make_float4(0.f, 0.f, 0.f, 0.f);
+                c4[0] = keep[0] ? q4.x : 0.f; c4[1] = keep[1] ? q4.y : 0.f; c4[2] = keep[2] ? q4.z : 0.f; c4[3] = keep[3] ? q4.w : 0.f;
+            } else for (int j = 0; j < 4; ++j) c4[j] = ld_kept(p + j, keep[j]);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 if (j >= nv) continue;
@@ -467,7 +490,7 @@ __global__ __launch_bounds__(256) void k_gather_box3(const IndexT* __restrict__ 
 
 template <typename ST>
 static int argmin_pass(const ST* ssd, const float* mesh, const float* u, float coef, bool coupled, int K, size_t v,
-                       unsigned long long* keys, bool arm, hipStream_t s) {
+                       unsigned long long* keys, bool arm, hipStream_t s, const unsigned char* cmask = nullptr) {
     if (arm && hipMemsetAsync(keys, 0xff, sizeof(unsigned long long) * v, s) != hipSuccess)
         return fail(CVX_ERR_LAUNCH, "argmin: memset failed");
     const bool vec4 = (v % 4 == 0) && ((reinterpret_cast<uintptr_t>(ssd) | reinterpret_cast<uintptr_t>(u)) & 15) == 0;
@@ -481,10 +504,10 @@ static int argmin_pass(const ST* ssd, const float* mesh, const float* u, float c
     nslices = cdiv(K, kslice);
     const dim3 grid(xb, nslices);
     if (vec4) {
-        if (coupled) hipLaunchKernelGGL((k_argmin4<true, ST>), grid, dim3(256), 0, s, ssd, mesh, u, coef, K, v, kslice, keys);
-        else hipLaunchKernelGGL((k_argmin4<false, ST>), grid, dim3(256), 0, s, ssd, mesh, u, coef, K, v, kslice, keys);
-    } else if (coupled) hipLaunchKernelGGL((k_argmin<true, ST>), grid, dim3(256), 0, s, ssd, mesh, u, coef, K, v, kslice, keys);
-    else hipLaunchKernelGGL((k_argmin<false, ST>), grid, dim3(256), 0, s, ssd, mesh, u, coef, K, v, kslice, keys);
+        if (coupled) hipLaunchKernelGGL((k_argmin4<true, ST>), grid, dim3(256), 0, s, ssd, mesh, u, coef, K, v, kslice, keys, cmask);
+        else hipLaunchKernelGGL((k_argmin4<false, ST>), grid, dim3(256), 0, s, ssd, mesh, u, coef, K, v, kslice, keys, cmask);
+    } else if (coupled) hipLaunchKernelGGL((k_argmin<true, ST>), grid, dim3(256), 0, s, ssd, mesh, u, coef, K, v, kslice, keys, cmask);
+    else hipLaunchKernelGGL((k_argmin<false, ST>), grid, dim3(256), 0, s, ssd, mesh, u, coef, K, v, kslice, keys, cmask);
     return check_last("argmin");
 }
 
@@ -494,18 +517,19 @@ static int argmin_pass(const ST* ssd, const float* mesh, const float* u, float c
 template <typename PrevT, typename ST>
 static int argmin_pass_pruned(const ST* ssd, const float* mesh, float* u, float coef, int K, int n, int h, int w, int d,
                               const float* smin, const PrevT* kprev, unsigned long long* list, int* list_count, int* next_count,
-                              unsigned long long* keys, const unsigned long long* minkeys, const Prob2& o, int nprob, hipStream_t s) {
+                              unsigned long long* keys, const unsigned long long* minkeys, const Prob2& o, int nprob, hipStream_t s,
+                              const unsigned char* cmask) {
     const size_t v = (size_t)h * w * d;
     const int refine = options().prune_refine != 0 ? 8 : 0x7fffffff;     // boxes above the per-thread limit get the second bound
     hipLaunchKernelGGL((k_argmin_voxel<PrevT, ST>), dim3((unsigned)cdiv64((int64_t)v, 64), nprob), dim3(64), 0, s, ssd, mesh, u, coef, K, n, h,
-                       w, d, smin, kprev, 8, list, list_count, next_count, keys, minkeys, refine, o);   // limit 8 = NB of the voxel kernel
+                       w, d, smin, kprev, 8, list, list_count, next_count, keys, minkeys, refine, o, cmask);   // limit 8 = NB of the voxel kernel
     // worst case bounded by one coalesced scan per pass: a chunk of 256 scattered reads moves about 8 KB, the scan K * v * 4 bytes
     const long long above = options().prune_stream_above >= 0 ? options().prune_stream_above : (long long)((double)K * (double)v / 2048.0);
     const int stream_above = (int)(above > 0x7fffffff ? 0x7fffffff : above);
     const int vec = (v % 4 == 0) && ((reinterpret_cast<uintptr_t>(ssd) | (uintptr_t)(o.ssd < 0 ? -o.ssd : o.ssd)) & 15) == 0;
     // voxels whose key the voxel kernel stored plainly keep it under the scan (it finds the same winner); listed voxels were armed to ~0
     hipLaunchKernelGGL((k_argmin_wave<PrevT, ST>), dim3(512, nprob), dim3(256), 0, s, ssd, mesh, u, coef, K, n, v, smin, kprev, list,
-                       list_count, keys, stream_above, vec, refine, o);
+                       list_count, keys, stream_above, vec, refine, o, cmask);
     return check_last("argmin_pruned");
 }
 
@@ -684,9 +708,16 @@ extern "C" size_t cvx_coupled_convex_workspace_bytes(int h, int w, int d, int di
 
 extern "C" int cvx_coupled_convex_f32(const float* ssd, const int64_t* argmin, const float* mesh, int h, int w, int d,
                                       int disp_hw, float* out, void* workspace, size_t workspace_bytes, void* stream) {
+    return cvx_coupled_convex_masked_f32(ssd, argmin, mesh, nullptr, h, w, d, disp_hw, out, workspace, workspace_bytes, stream);
+}
+
+extern "C" int cvx_coupled_convex_masked_f32(const float* ssd, const int64_t* argmin, const float* mesh, const unsigned char* cell_mask,
+                                             int h, int w, int d, int disp_hw, float* out, void* workspace, size_t workspace_bytes,
+                                             void* stream) {
     // the caller's `argmin` only seeds the first smoothing step (as in the reference); the lower bound of the pruned
-    // passes is taken from the volume itself
-    return cvx::coupled_convex_impl(ssd, false, argmin, mesh, h, w, d, disp_hw, out, /*argmin_is_exact=*/false, workspace, workspace_bytes, stream);
+    // passes is taken from the (masked) volume itself
+    return cvx::coupled_convex_impl(ssd, false, argmin, mesh, h, w, d, disp_hw, out, /*argmin_is_exact=*/false, workspace, workspace_bytes, stream,
+                                    cell_mask);
 }
 
 extern "C" int cvx_coupled_convex_f16(const void* ssd_half, const int64_t* argmin, const float* mesh, int h, int w, int d,
@@ -700,11 +731,13 @@ extern "C" int cvx_coupled_convex_f16(const void* ssd_half, const int64_t* argmi
 template <typename ST>
 static int coupled_core(const ST* ssd, const int64_t* argmin, const float* mesh, int h, int w, int d, int disp_hw, float* out,
                         bool argmin_is_exact, void* workspace, size_t workspace_bytes, const Prob2& o, int nprob, void* stream,
-                        bool counts_zeroed = false) {
+                        bool counts_zeroed = false, const unsigned char* cmask = nullptr) {
     // argmin == nullptr: the (cost, index) keys of the plain argmin pass sit in the first key buffer of the workspace
     const bool from_keys = argmin == nullptr;
     CVX_REQUIRE(ssd && mesh && out && workspace, "cvx_coupled_convex_f32: null pointer");
     CVX_REQUIRE(h > 0 && w > 0 && d > 0 && disp_hw >= 0, "cvx_coupled_convex_f32: bad arguments");
+    // a cell mask: the plain argmin of the UNMASKED volume says nothing about the masked one's minima, and the mask is one problem's
+    CVX_REQUIRE(!cmask || (!argmin_is_exact && argmin && nprob == 1), "coupled_convex: a cell mask needs the library's own minimum pass");
     if (workspace_bytes < cvx_coupled_convex_workspace_bytes(h, w, d, disp_hw))
         return fail(CVX_ERR_WORKSPACE, "cvx_coupled_convex_f32: workspace too small");
     hipStream_t s = as_stream(stream);
@@ -728,7 +761,7 @@ static int coupled_core(const ST* ssd, const int64_t* argmin, const float* mesh,
         if (from_keys) hipLaunchKernelGGL(k_keys_to_idx_min, gv, dim3(256), 0, s, keys[0], v, idx, smin, o);
         else if (argmin_is_exact) hipLaunchKernelGGL(k_gather_min<ST>, gv, dim3(256), 0, s, ssd, idx, v, smin, o);
         else {
-            int rc = argmin_pass(ssd, nullptr, nullptr, 0.0f, false, K, v, keys[0], true, s);   // per-voxel minimum of the volume
+            int rc = argmin_pass(ssd, nullptr, nullptr, 0.0f, false, K, v, keys[0], true, s, cmask);   // per-voxel minimum of the volume (a masked-out column: 0 at index 0)
             if (rc) return rc;
             hipLaunchKernelGGL(k_keys_to_min, dim3(gv.x), dim3(256), 0, s, keys[0], v, smin);
         }
@@ -739,8 +772,8 @@ static int coupled_core(const ST* ssd, const int64_t* argmin, const float* mesh,
             int rc;
             // keys[0] holds the library's own minimum pass unless the caller vouched for `argmin` (then idx IS the plain argmin)
             const unsigned long long* minkeys = (from_keys || !argmin_is_exact) ? keys[0] : nullptr;
-            if (it == 0) rc = argmin_pass_pruned<int, ST>(ssd, mesh, out, coeffs[it], K, n, h, w, d, smin, idx, list, counts + (it & 1), counts + ((it + 1) & 1), kc, minkeys, o, nprob, s);
-            else rc = argmin_pass_pruned<unsigned long long, ST>(ssd, mesh, out, coeffs[it], K, n, h, w, d, smin, keys[1 + ((it - 1) & 1)], list, counts + (it & 1), counts + ((it + 1) & 1), kc, minkeys, o, nprob, s);
+            if (it == 0) rc = argmin_pass_pruned<int, ST>(ssd, mesh, out, coeffs[it], K, n, h, w, d, smin, idx, list, counts + (it & 1), counts + ((it + 1) & 1), kc, minkeys, o, nprob, s, cmask);
+            else rc = argmin_pass_pruned<unsigned long long, ST>(ssd, mesh, out, coeffs[it], K, n, h, w, d, smin, keys[1 + ((it - 1) & 1)], list, counts + (it & 1), counts + ((it + 1) & 1), kc, minkeys, o, nprob, s, cmask);
             if (rc) return rc;
         }
         hipLaunchKernelGGL(k_gather_box3<unsigned long long>, gv, dim3(256), 0, s, keys[1 + (5 & 1)], mesh, K, h, w, d, out, (unsigned long long*)nullptr, (int*)nullptr, o);
@@ -751,7 +784,7 @@ static int coupled_core(const ST* ssd, const int64_t* argmin, const float* mesh,
     hipLaunchKernelGGL(k_gather_box3<int>, dim3(gv.x), dim3(256), 0, s, idx, mesh, K, h, w, d, out, keys[1], (int*)nullptr, o);
     static const float coeffs[6] = {0.003f, 0.01f, 0.03f, 0.1f, 0.3f, 1.0f};   // torch.tensor([...]) float32 (:98)
     for (int it = 0; it < 6; ++it) {
-        int rc = argmin_pass(ssd, mesh, out, coeffs[it], true, K, v, keys[it % 3], false, s);
+        int rc = argmin_pass(ssd, mesh, out, coeffs[it], true, K, v, keys[it % 3], false, s, cmask);
         if (rc) return rc;
         // the streamed passes need their key buffer re-armed two passes ahead
         hipLaunchKernelGGL(k_gather_box3<unsigned long long>, dim3(gv.x), dim3(256), 0, s, keys[it % 3], mesh, K, h, w, d, out,
@@ -761,9 +794,9 @@ static int coupled_core(const ST* ssd, const int64_t* argmin, const float* mesh,
 }
 
 int cvx::coupled_convex_impl(const void* ssd, bool f16, const int64_t* argmin, const float* mesh, int h, int w, int d, int disp_hw, float* out,
-                             bool argmin_is_exact, void* workspace, size_t workspace_bytes, void* stream) {
-    if (f16) return coupled_core(static_cast<const __half*>(ssd), argmin, mesh, h, w, d, disp_hw, out, argmin_is_exact, workspace, workspace_bytes, Prob2{0, 0, 0, 0}, 1, stream);
-    return coupled_core(static_cast<const float*>(ssd), argmin, mesh, h, w, d, disp_hw, out, argmin_is_exact, workspace, workspace_bytes, Prob2{0, 0, 0, 0}, 1, stream);
+                             bool argmin_is_exact, void* workspace, size_t workspace_bytes, void* stream, const unsigned char* cmask) {
+    if (f16) return coupled_core(static_cast<const __half*>(ssd), argmin, mesh, h, w, d, disp_hw, out, argmin_is_exact, workspace, workspace_bytes, Prob2{0, 0, 0, 0}, 1, stream, false, cmask);
+    return coupled_core(static_cast<const float*>(ssd), argmin, mesh, h, w, d, disp_hw, out, argmin_is_exact, workspace, workspace_bytes, Prob2{0, 0, 0, 0}, 1, stream, false, cmask);
 }
 
 // Forward and reverse direction of a pair in the same launches (the per-pass kernels are latency-bound at 30 000 voxels, so two

@@ -345,6 +345,34 @@ __device__ __forceinline__ float tri_sample(const Tri& t, const float* __restric
     return o;
 }
 
+// trilinear resize (ATen upsample_trilinear3d, align_corners=False): source taps and weights of output index o along one axis, and the
+// chain of three 1-D interpolations over the 8 taps v[(z, y, x)] (last dim first) -- shared by k_resize (pool.hip) and the rigid-fit
+// sampler that evaluates single voxels of the up-sampled field (rigidreg.hip)
+__device__ __forceinline__ void lin_coef(int o, int in, int out, int& i0, int& i1, float& l0, float& l1) {
+    if (in == out) { i0 = o; i1 = o; l0 = 1.0f; l1 = 0.0f; return; }
+    const float ratio = fdiv((float)in, (float)out);
+    float src = __builtin_fmaf(ratio, (float)o + 0.5f, -0.5f);
+    src = src < 0.0f ? 0.0f : src;
+    int a = (int)floorf(src);
+    a = a > in - 1 ? in - 1 : a;
+    float l = src - (float)a;
+    l = l < 0.f ? 0.f : (l > 1.f ? 1.f : l);
+    i0 = a;
+    i1 = a + ((a < in - 1) ? 1 : 0);
+    l1 = l;
+    l0 = 1.0f - l;
+}
+__device__ __forceinline__ float resize_chain(const float (&v)[8], float pre_mul, float lx0, float lx1, float ly0, float ly1, float lz0,
+                                              float lz1) {
+    const float a0 = __builtin_fmaf(v[0] * pre_mul, lx0, (v[1] * pre_mul) * lx1);   // pre_mul = 1: exact no-op
+    const float a1 = __builtin_fmaf(v[2] * pre_mul, lx0, (v[3] * pre_mul) * lx1);
+    const float b0 = __builtin_fmaf(v[4] * pre_mul, lx0, (v[5] * pre_mul) * lx1);
+    const float b1 = __builtin_fmaf(v[6] * pre_mul, lx0, (v[7] * pre_mul) * lx1);
+    const float l0 = __builtin_fmaf(a0, ly0, a1 * ly1);
+    const float l1 = __builtin_fmaf(b0, ly0, b1 * ly1);
+    return __builtin_fmaf(l0, lz0, l1 * lz1);
+}
+
 // Division of a WAVE-UNIFORM index by a launch constant on the scalar unit: q = mulhi(n, ceil(2^32 / d)) is exact whenever n * d < 2^32
 // (error term n (m d - 2^32) / (d 2^32) < 1 / d).  The compiler's own expansion of `tile / ntx` runs ~25 vector instructions per division
 // in every lane (the scalar unit has no divide) -- three of them opened k_warp_grad.
@@ -411,7 +439,8 @@ int adam_run_impl(const float* F2, const float* M2, int C, int h, int w, int d, 
 size_t adam_record_floats(int C, size_t V);            // floats of one feature record of the Adam loop: [CP/4][V + 1][4], CP = C rounded up to 4
 // convex.hip: coupled convex regularisation behind cvx_coupled_convex_f32 (argmin_is_exact: see there)
 int coupled_convex_impl(const void* ssd, bool f16, const int64_t* argmin, const float* mesh, int h, int w, int d, int disp_hw, float* out,
-                        bool argmin_is_exact, void* workspace, size_t workspace_bytes, void* stream);
+                        bool argmin_is_exact, void* workspace, size_t workspace_bytes, void* stream,
+                        const unsigned char* cmask = nullptr);   // cmask [h][w][d]: the passes see ssd * cmask (needs argmin_is_exact = false)
 int coupled_convex_dual_impl(const void* ssdA, const int64_t* argminA, float* outA, void* wsA, const void* ssdB, bool f16, const int64_t* argminB,
                              float* outB, void* wsB, const float* mesh, int h, int w, int d, int disp_hw, size_t workspace_bytes,
                              void* stream, bool counts_zeroed = false);   // counts_zeroed: the caller cleared CoupledWs::counts of both workspaces

@@ -620,3 +620,97 @@ extern "C" int cvx_register_pairs_f32(int n_pairs, const float* const* img_fixed
     g_side_slot = 0;
     return rc;
 }
+
+// ---- the convex stage of the CuRIOUS script in one call (l2r_2020_convexAdam_CuRIOUS.py:335-357) ------------------------------------
+// correlate -> coupled convex on the masked volume, for the reverse direction too when ic_iters > 0, inverse consistency with the
+// script's scale and flips, trilinear up-sampling: the operators cvx_register_pair_f32 chains with lambda_weight = 0, with the cell
+// masks, the caller's iteration count and caller-supplied coarse features.  The two directions run one after the other through ONE
+// cost volume (744 MB at the script's size); the exact correlation kernels, so every intermediate is the oracle's bit for bit.
+namespace cvx {
+struct StageWs {
+    float *ssd, *mesh, *soft, *soft2, *in1, *in2, *ic1, *ic2, *upin, *bh, *bw, *bd;
+    int64_t* argmin;
+    char *corr_ws, *conv_ws, *ic_ws;
+    size_t corr_bytes, conv_bytes, ic_bytes;
+};
+static StageWs stage_layout(Carver& cv, const cvx_convex_stage_params& p) {
+    const int n = 2 * p.disp_hw + 1;
+    const size_t v = (size_t)p.h * p.w * p.d, K = (size_t)n * n * n;
+    StageWs s{};
+    s.ssd = cv.take<float>(K * v);
+    s.argmin = cv.take<int64_t>(v);
+    s.mesh = cv.take<float>(3 * K);
+    s.soft = cv.take<float>(3 * v);
+    s.corr_bytes = cvx_correlate_workspace_bytes(p.C, p.h, p.w, p.d, p.disp_hw);
+    s.corr_ws = cv.take<char>(s.corr_bytes);
+    s.conv_bytes = cvx_coupled_convex_workspace_bytes(p.h, p.w, p.d, p.disp_hw);
+    s.conv_ws = cv.take<char>(s.conv_bytes);
+    if (p.ic_iters > 0) {
+        s.soft2 = cv.take<float>(3 * v);
+        s.in1 = cv.take<float>(3 * v); s.in2 = cv.take<float>(3 * v);
+        s.ic1 = cv.take<float>(3 * v); s.ic2 = cv.take<float>(3 * v);
+        s.upin = cv.take<float>(3 * v);
+        s.bh = cv.take<float>(p.h); s.bw = cv.take<float>(p.w); s.bd = cv.take<float>(p.d);
+        s.ic_bytes = cvx_inverse_consistency_workspace_bytes(p.h, p.w, p.d);
+        s.ic_ws = cv.take<char>(s.ic_bytes);
+    }
+    return s;
+}
+static int stage_params_ok(const cvx_convex_stage_params* p) {
+    CVX_REQUIRE(p, "cvx_convex_stage_f32: null parameters");
+    CVX_REQUIRE(p->reserved_[0] == 0 && p->reserved_[1] == 0 && p->reserved_[2] == 0 && p->reserved_[3] == 0,
+                "cvx_convex_stage_f32: reserved fields must be zero (struct laid out by a different header?)");
+    CVX_REQUIRE(p->C >= 1 && p->h >= 1 && p->w >= 1 && p->d >= 1 && p->disp_hw >= 0 && p->grid_sp >= 1 && p->ic_iters >= 0,
+                "cvx_convex_stage_f32: bad extent, search width, grid spacing or iteration count");
+    CVX_REQUIRE((double)(2 * p->disp_hw + 1) * (2 * p->disp_hw + 1) * (2 * p->disp_hw + 1) * ((double)p->h * p->w * p->d) < 2.0e9,
+                "cvx_convex_stage_f32: cost volume of more than 2e9 entries");
+    return CVX_OK;
+}
+}  // namespace cvx
+
+extern "C" size_t cvx_convex_stage_workspace_bytes(const cvx_convex_stage_params* p) {
+    if (stage_params_ok(p) != CVX_OK) return 0;
+    Carver m;
+    stage_layout(m, *p);
+    return ws_query(m);
+}
+
+extern "C" int cvx_convex_stage_f32(const float* feat_fix, const float* feat_mov, const unsigned char* mask_fix, const unsigned char* mask_mov,
+                                    const cvx_convex_stage_params* p, float* coarse_field, float* disp_hr, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
+    int rc = stage_params_ok(p);
+    if (rc) return rc;
+    CVX_REQUIRE(feat_fix && feat_mov && workspace && (coarse_field || disp_hr), "cvx_convex_stage_f32: null pointer");
+    CVX_REQUIRE(!disp_hr || (p->H >= 1 && p->W >= 1 && p->D >= 1), "cvx_convex_stage_f32: bad full-resolution extent");
+    if (workspace_bytes < cvx_convex_stage_workspace_bytes(p)) return fail(CVX_ERR_WORKSPACE, "cvx_convex_stage_f32: workspace too small");
+    const ContextScope scope(p->ctx);
+    hipStream_t s = as_stream(stream);
+    Carver cv(workspace);
+    const StageWs L = stage_layout(cv, *p);
+    const int h = p->h, w = p->w, d = p->d;
+    const size_t v = (size_t)h * w * d;
+    if ((rc = cvx_disp_mesh_f32(p->disp_hw, L.mesh, stream))) return rc;
+    // one direction: cost volume + plain argmin of the UNMASKED volume, then the six passes on the masked one (`ssd` is not written)
+    auto direction = [&](const float* a, const float* b, const unsigned char* mask, float* soft) -> int {
+        int r = cvx_correlate_ex_f32(a, b, p->C, h, w, d, p->disp_hw, nullptr, L.ssd, L.argmin, L.corr_ws, L.corr_bytes, stream);
+        if (r) return r;
+        return coupled_convex_impl(L.ssd, false, L.argmin, L.mesh, h, w, d, p->disp_hw, soft, /*argmin_is_exact=*/false, L.conv_ws, L.conv_bytes,
+                                   stream, mask);
+    };
+    if (p->ic_iters == 0) {                     // (:335-341) forward direction only
+        float* soft = coarse_field ? coarse_field : L.soft;
+        if ((rc = direction(feat_fix, feat_mov, mask_fix, soft))) return rc;
+        if (disp_hr && (rc = launch_resize(soft, 3, h, w, d, disp_hr, p->H, p->W, p->D, (float)p->grid_sp, 1.0f, s))) return rc;
+        return check_last("convex_stage");
+    }
+    if ((rc = direction(feat_fix, feat_mov, mask_fix, L.soft))) return rc;
+    if ((rc = direction(feat_mov, feat_fix, mask_mov, L.soft2))) return rc;          // (:348-350)
+    if ((rc = cvx_affine_base_f32(h, L.bh, stream)) || (rc = cvx_affine_base_f32(w, L.bw, stream)) || (rc = cvx_affine_base_f32(d, L.bd, stream))) return rc;
+    const dim3 gv((unsigned)cdiv64((int64_t)v, 256));
+    hipLaunchKernelGGL(k_ic_prepare, dim3(gv.x, 2), dim3(256), 0, s, L.soft, L.soft2, h, w, d, L.in1, L.in2);          // (disp_soft / scale).flip(1)   (:351)
+    if ((rc = cvx_inverse_consistency_f32(L.in1, L.in2, h, w, d, p->ic_iters, L.bh, L.bw, L.bd, L.ic1, L.ic2, L.ic_ws, L.ic_bytes, stream))) return rc;
+    float* up = coarse_field ? coarse_field : L.upin;
+    hipLaunchKernelGGL(k_ic_finish, gv, dim3(256), 0, s, L.ic1, h, w, d, (float)p->grid_sp, up);                       // disp_ice.flip(1) * scale * grid_sp   (:354)
+    if (disp_hr && (rc = launch_resize(up, 3, h, w, d, disp_hr, p->H, p->W, p->D, 1.0f, 1.0f, s))) return rc;
+    return check_last("convex_stage");
+}

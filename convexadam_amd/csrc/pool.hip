@@ -324,20 +324,7 @@ __global__ __launch_bounds__(256) void k_select(const float* __restrict__ m, con
 // ---- trilinear resize (ATen upsample_trilinear3d, align_corners=False) ----------------------------
 //   src = max(fma(in/out, dst + 0.5, -0.5), 0); i0 = min(floor(src), in-1); l1 = clamp(src - i0, 0, 1)
 //   l0 = 1 - l1; i1 = i0 + (i0 < in-1); per level (last dim first): r = fma(v0, l0, v1 * l1)
-__device__ __forceinline__ void lin_coef(int o, int in, int out, int& i0, int& i1, float& l0, float& l1) {
-    if (in == out) { i0 = o; i1 = o; l0 = 1.0f; l1 = 0.0f; return; }
-    const float ratio = fdiv((float)in, (float)out);
-    float src = __builtin_fmaf(ratio, (float)o + 0.5f, -0.5f);
-    src = src < 0.0f ? 0.0f : src;
-    int a = (int)floorf(src);
-    a = a > in - 1 ? in - 1 : a;
-    float l = src - (float)a;
-    l = l < 0.f ? 0.f : (l > 1.f ? 1.f : l);
-    i0 = a;
-    i1 = a + ((a < in - 1) ? 1 : 0);
-    l1 = l;
-    l0 = 1.0f - l;
-}
+// (lin_coef and resize_chain live in cvx_common.h: rigidreg.hip evaluates single voxels of a resize with them)
 // One thread per output voxel, all channels.  CT > 0: the channel count at compile time (fields: 3) -- the channel loop is
 // unrolled and the 8 * CT taps are in flight together; with a run-time count the loop runs one memory round trip per channel
 // and the kernel is bound by that latency (59 vs 3x us for the 82 MB field of the final up-sampling).
@@ -359,13 +346,7 @@ __global__ __launch_bounds__(256) void k_resize(const float* __restrict__ in, in
                  o11 = ((size_t)z1 * w + y1) * d;
     const size_t cs = (size_t)h * w * d;
     auto one = [&](const float (&v)[8]) {
-        const float a0 = __builtin_fmaf(v[0] * pre_mul, lx0, (v[1] * pre_mul) * lx1);   // pre_mul = 1: exact no-op
-        const float a1 = __builtin_fmaf(v[2] * pre_mul, lx0, (v[3] * pre_mul) * lx1);
-        const float b0 = __builtin_fmaf(v[4] * pre_mul, lx0, (v[5] * pre_mul) * lx1);
-        const float b1 = __builtin_fmaf(v[6] * pre_mul, lx0, (v[7] * pre_mul) * lx1);
-        const float l0 = __builtin_fmaf(a0, ly0, a1 * ly1);
-        const float l1 = __builtin_fmaf(b0, ly0, b1 * ly1);
-        float r = __builtin_fmaf(l0, lz0, l1 * lz1);
+        float r = resize_chain(v, pre_mul, lx0, lx1, ly0, ly1, lz0, lz1);
         if (post_div != 1.0f) r = fdiv(r, post_div);
         return r;
     };

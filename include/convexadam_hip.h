@@ -221,6 +221,17 @@ size_t cvx_coupled_convex_workspace_bytes(int h, int w, int d, int disp_hw);
 int cvx_coupled_convex_f32(const float* ssd, const int64_t* argmin, const float* mesh, int h, int w, int d,
                            int disp_hw, float* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* the same solve on ssd * cell_mask[None] (l2r_2020_convexAdam_CuRIOUS.py:336-338,349-350), bit for bit, WITHOUT writing `ssd` and
+ *   without a masked copy of it: cell_mask [h][w][d] bytes (device), non-zero = keep the cell; NULL = cvx_coupled_convex_f32.
+ *   `argmin` is the plain argmin of the UNMASKED volume (the script masks after correlate has returned it) and seeds the first
+ *   smoothing step only; the library's own minimum pass sees a masked-out column as K zeros (minimum 0 at index 0).
+ *   Non-finite input: the columns of masked-out cells are never read, so a NaN or inf there does not reach the result, where
+ *   torch's ssd * 0 would make the column NaN -- finite features cannot produce one.  Kept cells behave as in the unmasked
+ *   operator, its NaN rule included. */
+int cvx_coupled_convex_masked_f32(const float* ssd, const int64_t* argmin, const float* mesh, const unsigned char* cell_mask,
+                                  int h, int w, int d, int disp_hw, float* out, void* workspace, size_t workspace_bytes,
+                                  void* stream);
+
 /* the same solve on a half-precision cost volume (cvx_corr_opts.f16 = 2): values are widened to float32 on load (exact) */
 int cvx_coupled_convex_f16(const void* ssd_half, const int64_t* argmin, const float* mesh, int h, int w, int d,
                            int disp_hw, float* out, void* workspace, size_t workspace_bytes, void* stream);
@@ -547,6 +558,46 @@ int cvx_rigid_lts_f32(const float* fixed, int ld_fixed, const float* moving, int
  *                        -> out [C][ho][wo][do]; bit-identical to ATen's CPU affine_grid + grid_sample in float32 */
 int cvx_affine_warp_f32(const float* vol, int C, int h, int w, int d, const float* theta, int ho, int wo, int dd, int mode, float* out,
                         void* stream);
+
+/* rigid registration around the convex stage (csrc/rigidreg.hip, l2r_2020_convexAdam_CuRIOUS.py) -------------------------------------
+ * cvx_threshold_pool_mask_u8 : F.avg_pool3d((img > thresh).float(), g, stride=g) > .5 (:328,330): img [H][W][D] -> mask [H/g][W/g][D/g]
+ *                        bytes 0 / 1 (floor division, remainder voxels ignored); the integer rule 2 * count > g^3, equal to the float
+ *                        expression for 1 <= g <= 64.  A NaN voxel compares false, as in torch.
+ * cvx_label_centroids_i64 : acc [max_label + 1][4] (device) = per label l the number of voxels with (int)seg == l and the sums of their
+ *                        indices along H, W and D (the columns of mesh[:, idx], :312-316): exact integer sums, identical on every run.
+ *                        Values outside [0, max_label] and NaN are skipped; 0 <= max_label < 1024.  The centroid sums / count and the
+ *                        script's TRE are formed by the caller in float64 (a label with count 0 has no centroid). */
+int cvx_threshold_pool_mask_u8(const float* img, int H, int W, int D, float thresh, int g, unsigned char* mask, void* stream);
+int cvx_label_centroids_i64(const float* seg, int H, int W, int D, int max_label, int64_t* acc, void* stream);
+/* cvx_convex_stage_f32 : the script's convex stage (:335-357) in one call: correlate -> coupled convex on the masked cost volume, in
+ *                        both directions when ic_iters > 0 (the forward volume masked by mask_fix, the reverse one by mask_mov),
+ *                        inverse consistency with scale = (size' - 1) / 2 and the script's flips, F.interpolate(.., size=(H, W, D),
+ *                        trilinear, align_corners=False).  float32 in the reference's evaluation order (the exact correlation kernels);
+ *                        the two directions share one cost volume, which is never multiplied by a mask.  A NULL mask keeps every cell. */
+typedef struct cvx_convex_stage_params {
+    int C, h, w, d;          /* coarse feature extent */
+    int disp_hw, grid_sp;
+    int ic_iters;            /* 0: forward direction only (:335-341); > 0: reverse pass + that many IC steps (:348-354; the script: 5) */
+    int H, W, D;             /* extent of the full-resolution field */
+    const cvx_context* ctx;
+    int reserved_[4];        /* must be zero */
+} cvx_convex_stage_params;
+size_t cvx_convex_stage_workspace_bytes(const cvx_convex_stage_params* p);
+int cvx_convex_stage_f32(const float* feat_fix, const float* feat_mov,            /* [C][h][w][d] */
+                         const unsigned char* mask_fix, const unsigned char* mask_mov,   /* [h][w][d] or NULL */
+                         const cvx_convex_stage_params* p,
+                         float* coarse_field,  /* [3][h][w][d]: disp_soft (ic_iters 0) or disp_ice.flip(1)*scale*grid_sp, may be NULL */
+                         float* disp_hr,       /* [3][H][W][D] voxels, may be NULL */
+                         void* workspace, size_t workspace_bytes, void* stream);
+/* cvx_rigid_samples_f32 : the rows T1, T2 (:359-365; M x 4, ones column included) of the kept coarse cells in torch.nonzero order, computed
+ *                        from the COARSE field [3][h][w][d] (voxels; what cvx_convex_stage_f32 returns with ic_iters > 0): per cell the
+ *                        eight full-resolution corner voxels of the sample point, each corner's displacement by the interpolation chain
+ *                        of cvx_resize_trilinear_f32, ident + disp.flip / (size - 1) * 2 in the reference's order, the weights and corner
+ *                        order of cvx_grid_sample_f32 -- bit-identical to sampling the up-sampled field, which is never formed.  T1, T2
+ *                        (device) must hold h * w * d rows; *count_host receives M.  SYNCHRONISES `stream` once (M reaches the host). */
+size_t cvx_rigid_samples_workspace_bytes(int h, int w, int d, int H, int W, int D);
+int cvx_rigid_samples_f32(const float* coarse_field, const unsigned char* mask, int h, int w, int d, int H, int W, int D, float* T1,
+                          float* T2, int64_t* count_host, void* workspace, size_t workspace_bytes, void* stream);
 
 #pragma GCC visibility pop
 
