@@ -133,6 +133,42 @@ def extract_features(img_fixed: torch.Tensor, img_moving: torch.Tensor, mind_r: 
     return features_fix, features_mov
 
 
+# ---- what the three device entry points share ----------------------------------------------------------------------------------------
+def _unpack_pair(img_fixed, img_moving, feat_fixed, feat_moving, shape_error=None):
+    """Two (H,W,D) images or two (C,H,W,D) feature volumes -> (a, b, ff, fm, n_feat, H, W, D, dev); the pair not given is None.  `shape_error`:
+    text of the ValueError for images that are not two 3-D volumes of equal shape (None: not checked here)."""
+    if feat_fixed is not None:
+        ff, fm = f32c(feat_fixed), f32c(feat_moving)
+        n_feat = int(ff.shape[0])
+        H, W, D = [int(s) for s in ff.shape[1:]]
+        return None, None, ff, fm, n_feat, H, W, D, ff.device
+    a, b = f32c(img_fixed), f32c(img_moving)
+    if shape_error is not None and (a.dim() != 3 or a.shape != b.shape):
+        raise ValueError(shape_error)
+    H, W, D = [int(s) for s in a.shape]
+    return a, b, None, None, 0, H, W, D, a.device
+
+
+def _pair_params(adam_mode, cost="ssd", corr_mode="exact", storage="fp32", **fields):
+    """struct cvx_pair_params, every field by name; a field left out stays 0, which the library reads as its default."""
+    fields = {k: float(v) if k in ("lambda_weight", "cost_scale") else int(v) for k, v in fields.items()}
+    return PairParams(cost=1 if cost == "sad" else 0, corr_fast=1 if corr_mode == "fast" else 0, fp16_storage=1 if storage == "fp16" else 0,
+                      adam_fast={"exact": 0, "fast": 1, "fast_all": 2}[adam_mode], **fields)
+
+
+def _workspace_bytes(query, *args, otherwise=""):
+    """Result of a workspace-size query of the library; 0 = arguments it refuses -> CvxError with its message."""
+    nws = query(*args)
+    if nws == 0:
+        raise _lib.CvxError(_lib.CVX_ERR_INVALID_ARG, lib().cvx_last_error().decode() or otherwise)
+    return nws
+
+
+def _field_shape(H, W, D, grid_sp, ic, lambda_weight):
+    """Full resolution, or the coarse grid for the reference's ic=False & lambda_weight<=0 case."""
+    return (3, H, W, D) if ic or lambda_weight > 0 else (3, H // grid_sp, W // grid_sp, D // grid_sp)
+
+
 def register_pair_device(img_fixed=None, img_moving=None, feat_fixed=None, feat_moving=None, mind_r=1, mind_d=2,
                          lambda_weight=1.25, grid_sp=6, disp_hw=4, selected_niter=80, selected_smooth=0, grid_sp_adam=2,
                          ic=True, cost_scale=12.0, out=None, profile=None, cost="ssd", n_box=2, n_spline_pools=3, corr_mode="exact",
@@ -144,20 +180,8 @@ def register_pair_device(img_fixed=None, img_moving=None, feat_fixed=None, feat_
     (task 3 :191); corr_mode="fast" = FMA / separable correlation sums; storage="fp16" = pooled features and cost volume rounded to
     half precision with float32 accumulation (the reference's GPU default dtype, convex_adam_MIND.py:79); adam_mode="fast" = the
     Adam loop in throughput arithmetic (cvx_adam_run_fast_f32; same mathematics, graded by end-point error, not by bits)."""
-    if feat_fixed is not None:
-        ff, fm = f32c(feat_fixed), f32c(feat_moving)
-        n_feat = int(ff.shape[0])
-        H, W, D = [int(s) for s in ff.shape[1:]]
-        dev = ff.device
-        a = b = None
-    else:
-        a, b = f32c(img_fixed), f32c(img_moving)
-        if a.dim() != 3 or a.shape != b.shape:
-            raise ValueError("register_pair_device expects two (H,W,D) volumes of equal shape")
-        H, W, D = [int(s) for s in a.shape]
-        dev = a.device
-        ff = fm = None
-        n_feat = 0
+    a, b, ff, fm, n_feat, H, W, D, dev = _unpack_pair(img_fixed, img_moving, feat_fixed, feat_moving,
+                                                      "register_pair_device expects two (H,W,D) volumes of equal shape")
     _require_hip(dev)
     if lambda_weight > 0 and selected_niter < 1:
         # the reference reads `disp_sample` after a loop that never ran (:181)
@@ -177,16 +201,12 @@ def register_pair_device(img_fixed=None, img_moving=None, feat_fixed=None, feat_
     adam_mode = _resolve_adam_mode(adam_mode, n_spline_pools, storage)
     if cost not in ("ssd", "sad") or corr_mode not in ("exact", "fast") or storage not in ("fp32", "fp16") or adam_mode not in ("exact", "fast", "fast_all"):
         raise ValueError("cost must be 'ssd' or 'sad', corr_mode 'exact' or 'fast', adam_mode 'exact', 'fast' or 'fast_all', storage 'fp32' or 'fp16'")
-    p = PairParams(H, W, D, int(mind_r), int(mind_d), float(lambda_weight), int(grid_sp), int(disp_hw), int(selected_niter),
-                   int(selected_smooth), int(grid_sp_adam), 1 if ic else 0, n_feat, float(cost_scale), 1 if cost == "sad" else 0,
-                   int(n_box), int(n_spline_pools), 1 if corr_mode == "fast" else 0, 1 if storage == "fp16" else 0)
-    p.adam_fast = {"exact": 0, "fast": 1, "fast_all": 2}[adam_mode]
+    p = _pair_params(adam_mode, cost, corr_mode, storage, H=H, W=W, D=D, mind_r=mind_r, mind_d=mind_d, lambda_weight=lambda_weight, grid_sp=grid_sp,
+                     disp_hw=disp_hw, selected_niter=selected_niter, selected_smooth=selected_smooth, grid_sp_adam=grid_sp_adam, ic=bool(ic),
+                     n_feat=n_feat, cost_scale=cost_scale, n_box=n_box, n_spline_pools=n_spline_pools)
     L = lib()
-    nws = L.cvx_register_pair_workspace_bytes(C.byref(p))
-    if nws == 0:
-        raise _lib.CvxError(_lib.CVX_ERR_INVALID_ARG, L.cvx_last_error().decode())
-    full = ic or lambda_weight > 0
-    oshape = (3, H, W, D) if full else (3, H // grid_sp, W // grid_sp, D // grid_sp)
+    nws = _workspace_bytes(L.cvx_register_pair_workspace_bytes, C.byref(p))
+    oshape = _field_shape(H, W, D, grid_sp, ic, lambda_weight)
     if out is None:
         out = torch.empty(oshape, dtype=torch.float32, device=dev)
     ws = workspace(nws, dev)
@@ -207,24 +227,18 @@ def register_pair_snapshots_device(img_fixed=None, img_moving=None, feat_fixed=N
     (1-based), once per entry of `smooths` (0 = as is, k = three k^3 mean filters) -> (n_snap, n_smooth, 3, H, W, D) device tensor.
     The default is the 9-field variant of self_configuring/convex_adam_MIND.py:115-139; the sweep's stage 2 evaluates iterations
     60 / 80 / 100 / 120 of one 120-iteration run the same way (adam_run_withconfig_shiftSpline.py:234-246)."""
-    if feat_fixed is not None:
-        ff, fm = f32c(feat_fixed), f32c(feat_moving)
-        n_feat = int(ff.shape[0]); H, W, D = [int(v) for v in ff.shape[1:]]; dev = ff.device; a = b = None
-    else:
-        a, b = f32c(img_fixed), f32c(img_moving)
-        H, W, D = [int(v) for v in a.shape]; dev = a.device; ff = fm = None; n_feat = 0
+    a, b, ff, fm, n_feat, H, W, D, dev = _unpack_pair(img_fixed, img_moving, feat_fixed, feat_moving)
     _require_hip(dev)
     its = [int(v) for v in snapshot_iters]
     sms = [int(v) for v in smooths]
-    p = PairParams(H, W, D, int(mind_r), int(mind_d), float(lambda_weight), int(grid_sp), int(disp_hw), its[-1], 0, int(grid_sp_adam),
-                   1 if ic else 0, n_feat, float(cost_scale), 0, 0, int(n_spline_pools), 0, 0)
-    p.adam_fast = {"exact": 0, "fast": 1, "fast_all": 2}[_resolve_adam_mode(adam_mode, n_spline_pools)]
+    p = _pair_params(_resolve_adam_mode(adam_mode, n_spline_pools), H=H, W=W, D=D, mind_r=mind_r, mind_d=mind_d, lambda_weight=lambda_weight,
+                     grid_sp=grid_sp, disp_hw=disp_hw, selected_niter=its[-1], grid_sp_adam=grid_sp_adam, ic=bool(ic), n_feat=n_feat,
+                     cost_scale=cost_scale, n_spline_pools=n_spline_pools)
     L = lib()
     it_arr = (C.c_int * len(its))(*its)
     sm_arr = (C.c_int * len(sms))(*sms)
-    nws = L.cvx_register_pair_snapshots_workspace_bytes(C.byref(p), len(its), C.cast(sm_arr, C.c_void_p), len(sms))
-    if nws == 0:
-        raise _lib.CvxError(_lib.CVX_ERR_INVALID_ARG, L.cvx_last_error().decode() or "bad snapshot arguments")
+    nws = _workspace_bytes(L.cvx_register_pair_snapshots_workspace_bytes, C.byref(p), len(its), C.cast(sm_arr, C.c_void_p), len(sms),
+                           otherwise="bad snapshot arguments")
     out = torch.empty((len(its), len(sms), 3, H, W, D), dtype=torch.float32, device=dev)
     ws = workspace(nws, dev)
     with torch.cuda.device(dev):
@@ -246,19 +260,15 @@ def register_pairs_device(imgs_fixed, imgs_moving, outs=None, n_streams=2, mind_
     _require_hip(dev)
     if lambda_weight > 0 and selected_niter < 1:
         raise UnboundLocalError("local variable 'disp_sample' referenced before assignment (convex_adam_MIND.py:181)")
-    p = PairParams(H, W, D, int(mind_r), int(mind_d), float(lambda_weight), int(grid_sp), int(disp_hw), int(selected_niter),
-                   int(selected_smooth), int(grid_sp_adam), 1 if ic else 0, 0, float(cost_scale))
-    p.adam_fast = {"exact": 0, "fast": 1, "fast_all": 2}[_resolve_adam_mode(adam_mode)]
+    p = _pair_params(_resolve_adam_mode(adam_mode), H=H, W=W, D=D, mind_r=mind_r, mind_d=mind_d, lambda_weight=lambda_weight, grid_sp=grid_sp,
+                     disp_hw=disp_hw, selected_niter=selected_niter, selected_smooth=selected_smooth, grid_sp_adam=grid_sp_adam, ic=bool(ic),
+                     cost_scale=cost_scale)
     L = lib()
-    per = L.cvx_register_pair_workspace_bytes(C.byref(p))
-    if per == 0:
-        raise _lib.CvxError(_lib.CVX_ERR_INVALID_ARG, L.cvx_last_error().decode())
+    per = _workspace_bytes(L.cvx_register_pair_workspace_bytes, C.byref(p))
     n_streams = max(1, min(int(n_streams), n, 8))
     nws = ((per + 4095) // 4096 * 4096) * n_streams
-    full = ic or lambda_weight > 0
-    oshape = (3, H, W, D) if full else (3, H // grid_sp, W // grid_sp, D // grid_sp)
     if outs is None:
-        outs = [torch.empty(oshape, dtype=torch.float32, device=dev) for _ in range(n)]
+        outs = [torch.empty(_field_shape(H, W, D, grid_sp, ic, lambda_weight), dtype=torch.float32, device=dev) for _ in range(n)]
     ws = workspace(nws, dev)
     arr = lambda ts: (C.c_void_p * n)(*[t.data_ptr() for t in ts])
     dims = (C.c_int * 3)()

@@ -29,8 +29,8 @@ int check_last(const char* what) {
     return CVX_OK;
 }
 
-static long long env_ll(const char* name, long long dflt) {
-    const char* e = getenv(name);
+static long long env_ll(const char* name, long long dflt) {       // (name == nullptr: an option without a variable)
+    const char* e = name ? getenv(name) : nullptr;
     return e ? atoll(e) : dflt;
 }
 
@@ -50,13 +50,9 @@ struct cvx_context {
     int tbl_device = -1;                       // device the owned tables live on
 };
 namespace cvx {
-static Options env_options() {
-    return {env_ll("CVX_MIND_TILED", 0),   env_ll("CVX_MIND_OVERLAP", 0),  env_ll("CVX_MM_TX", 0),        env_ll("CVX_MM_SLOTS", 512),          env_ll("CVX_BOX_TILED", 0),
-            env_ll("CVX_NO_PRUNE", 0),     env_ll("CVX_CORR_UNFUSED", 0), env_ll("CVX_CORR_FUSED_ALL", 0), env_ll("CVX_PRUNE_STREAM_ABOVE", -1), env_ll("CVX_CF_CENSUS", 0), env_ll("CVX_CF_PRIO", 136),
-            env_ll("CVX_WARP_FLAT", 0),    env_ll("CVX_BOX_YT", 8),       env_ll("CVX_BOX_WG_TARGET", 0),
-            env_ll("CVX_BOX_XSPLIT", -1),  env_ll("CVX_BOX_CPT", 4),      env_ll("CVX_BOX_UNEVEN", 200), env_ll("CVX_BOX_ADAM_ROLE", 0), env_ll("CVX_BOX_DPP", 0),      env_ll("CVX_BOX_PK", 0),       env_ll("CVX_BOX_PRIO", 0),     env_ll("CVX_LABEL_POW_BLOCK", 32), 0,                             env_ll("CVX_MIND_MEAN_THREADS", 0),
-            env_ll("CVX_EDT_SEQUENTIAL", 0), env_ll("CVX_WARP_OCTANT", 4), env_ll("CVX_BOX_FWD_TILE", -1), env_ll("CVX_BOX_BWD_TILE", -1), env_ll("CVX_BOX_WALK", 1), env_ll("CVX_CORR_DUAL", 0), env_ll("CVX_PRUNE_REFINE", 1), env_ll("CVX_MIND_RECORDS", 1), env_ll("CVX_RESIZE_UP2", 1), env_ll("CVX_MIND_BLOCKED", 1), env_ll("CVX_CORR_CERT", 1), env_ll("CVX_CC_DEBUG", 0), env_ll("CVX_IC_FUSED", 0), env_ll("CVX_MIND_SINGLE", 0), env_ll("CVX_MS_ZLEN", 0), env_ll("CVX_CF_MAP", 1), env_ll("CVX_CERT_UNFUSED", 0), env_ll("CVX_FBOX_TILE", 0), env_ll("CVX_BOX_TILE_SYNC", 0), env_ll("CVX_BOX_PREDIV", 1), 0};
-}
+#define X(name, env, dflt) env_ll(env, dflt),
+static Options env_options() { return {CVX_OPTIONS(X)}; }         // (in the order of the fields: both are expansions of the one list)
+#undef X
 static cvx_context& default_context() {
     static cvx_context c = [] { cvx_context d; d.opt = env_options(); return d; }();
     return c;
@@ -113,13 +109,9 @@ __global__ __launch_bounds__(256) void k_expf(const float* __restrict__ x, float
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) out[i] = cvx_expf(x[i]);
 }
 struct OptName { const char* name; long long Options::*field; };
-static const OptName kOptNames[] = {{"mind_tiled", &Options::mind_tiled},     {"mind_overlap", &Options::mind_overlap},   {"mm_tx", &Options::mm_tx},
-                                    {"mm_slots", &Options::mm_slots},         {"box_tiled", &Options::box_tiled},
-                                    {"no_prune", &Options::no_prune},         {"corr_unfused", &Options::corr_unfused}, {"corr_fused_all", &Options::corr_fused_all},
-                                    {"prune_stream_above", &Options::prune_stream_above}, {"cf_census", &Options::cf_census}, {"cf_prio", &Options::cf_prio},
-                                    {"warp_flat", &Options::warp_flat},       {"box_yt", &Options::box_yt},             {"box_wg_target", &Options::box_wg_target},
-                                    {"box_xsplit", &Options::box_xsplit},     {"box_cpt", &Options::box_cpt},           {"box_uneven", &Options::box_uneven},     {"box_adam_role", &Options::box_adam_role}, {"box_dpp", &Options::box_dpp},           {"box_pk", &Options::box_pk},             {"box_prio", &Options::box_prio},         {"label_pow_block", &Options::label_pow_block}, {"census_ptr", &Options::census_ptr},     {"mind_mean_threads", &Options::mind_mean_threads},
-                                    {"edt_sequential", &Options::edt_sequential}, {"warp_octant", &Options::warp_octant}, {"box_fwd_tile", &Options::box_fwd_tile}, {"box_bwd_tile", &Options::box_bwd_tile}, {"box_walk", &Options::box_walk}, {"corr_dual", &Options::corr_dual}, {"prune_refine", &Options::prune_refine}, {"mind_records", &Options::mind_records}, {"resize_up2", &Options::resize_up2}, {"mind_blocked", &Options::mind_blocked}, {"corr_cert", &Options::corr_cert}, {"cc_debug", &Options::cc_debug}, {"ic_fused", &Options::ic_fused}, {"mind_single", &Options::mind_single}, {"ms_zlen", &Options::ms_zlen}, {"cf_map", &Options::cf_map}, {"cert_unfused", &Options::cert_unfused}, {"fbox_tile", &Options::fbox_tile}, {"box_tile_sync", &Options::box_tile_sync}, {"box_prediv", &Options::box_prediv}, {"tile_census_ptr", &Options::tile_census_ptr}};
+#define X(name, env, dflt) {#name, &Options::name},
+static const OptName kOptNames[] = {CVX_OPTIONS(X)};
+#undef X
 
 }  // namespace cvx
 

@@ -59,80 +59,83 @@ static inline size_t ws_query(const Carver& m) { return m.used ? m.used + 256 : 
 // One table per context (cvx_context_*); the default context is initialised once from the environment (CVX_<NAME IN CAPITALS>, e.g.
 // CVX_MIND_TILED=1) and changeable through cvx_set_option(); every selectable path except mind_mean_threads is bit-identical, the
 // switches exist for A/B timing and so that the test-suite can run every variant (tests/test_gpu_parity.py::test_kernel_variants_agree).
-struct Options {
-    long long mind_tiled;          // 1: tiled MIND stencil instead of the z-marching one
-    long long mind_overlap;        // 1: the whole-pair pipeline runs the moving image's descriptor pass on a side stream beside the fixed one's (measured: no gain)
-    long long mm_tx;               // 32 / 64: tile width of the marching MIND stencil (0 = automatic)
-    long long mm_slots;            // workgroup budget of the marching MIND stencil (512)
-    long long box_tiled;           // 1: tiled three-box kernels of the Adam loop instead of the z-marching ones
-    long long no_prune;            // 1: streaming coupled-convex passes instead of branch and bound
-    long long corr_unfused;        // 1: k_corr_raw + k_corr_box2 instead of the fused correlation kernel
-    long long corr_fused_all;      // 1: the fused correlation kernel also for C >= 16 (default there: the round-1 kernels, which are faster)
-    long long prune_stream_above;  // pruned pass falls back to a coalesced scan above this many 256-displacement chunks (-1 = K*v/2048)
-    long long cf_census;           // 1: the fused correlation kernel records per-workgroup residency in its workspace
-    long long cf_prio;             // fused correlation kernel: issue priorities (s_setprio, 0..3) as four base-4 digits -- first-round workgroup raw / box,
-                                   //    second-round workgroup raw / box (two workgroups share a CU; 136 = 2,0,2,0: the raw stage above the boxes)
-    long long warp_flat;           // 1: flat 64-bit gathers in k_warp_grad instead of buffer loads
-    long long box_yt;              // rows per tile of the marching three-box kernels: 8 (default) or 4
-    long long box_wg_target;       // workgroups the z-marching three-box kernels of the Adam loop aim for (z-chunk length follows); 0 = automatic
-    long long box_xsplit;          // x tiles of the marching three-box kernels: -1 automatic (rows > 62 columns: tiles of <= 56), 0 off
-    long long box_cpt;             // output columns per thread of the marching three-box kernels: 4, or 2 (x tiles / rows <= 62 columns only)
-    long long box_uneven;          // marching three-box kernels with two workgroups per CU: length ratio (percent) of the z chunks given to the first and
-                                   //    to the second dispatch round (boxmarch.hip, BMTable); <= 100: equal chunks
-    long long box_adam_role;       // adjoint + Adam kernel: 1 = the Adam update runs as a fourth role (two extra wavefronts) instead of inside every wavefront's step
-    long long box_dpp;             // marching three-box kernels, x-tile path: 1 = halo columns through DPP lane shifts instead of a second LDS read per row
-    long long box_pk;              // marching three-box kernels: 1 = the two running sums of a column as one register pair (v_pk_add_f32 with a broadcast tap)
-    long long box_prio;            // marching three-box kernels: 1 / 2 = the workgroups sharing a CU alternate their issue priority step by step
-    long long label_pow_block;     // cvx_label_weights_host: elements per vectorised block of the reference host's torch.pow (32: AVX-512 build, the golden host; 16: AVX2)
-    long long census_ptr;          // debugging aid: device address of a uint64 buffer; the Adam-loop kernels record per workgroup
-                                   //    {start, first data, end} in 100 MHz ticks (s_memrealtime) + placement there (0 = off)
-    long long mind_mean_threads;   // 0: exactly rounded global mean in MINDSSC (default); T > 0: torch's own float sum with T threads
-                                   //    (reference-bits mode; NOT a bit-identical variant -- it changes the clamp bounds by ulps)
-    long long edt_sequential;      // 1: squared distance transform with the sequential lower-envelope passes (one thread per line) instead of the tiled outward search
-    long long warp_octant;         // adam_mode "fast" warp kernel, tile order inside an XCD's share: G >= 2 (default 4) = x fastest, then G z-adjacent tiles, then y (the tiles that share planes follow each other: FETCH_SIZE -13 %, 5.64 -> 5.59 ms per pair); 0 = plain slabs (x, y, z); 1 = one octant of the tile grid per XCD (measured: no gain)
-    long long box_fwd_tile;        // forward three-box pass of the Adam loop: -1 = automatic (tiles of boxtile.hip where they fill the chip), 0 = z-marching pipeline (boxmarch.hip), kind * 1000 + segments = a tile kernel variant (boxtile.hip; bit-identical)
-    long long box_bwd_tile;        // adjoint three-box pass (+ Adam update) of the exact Adam loop: as box_fwd_tile (-1 automatic, 0 = z-marching pipeline, kind * 1000 + segments)
-    long long box_walk;            // 1 (default): single zero-padded box filters (sweep smoothers, final smoothing) through the z-walking kernel; 0 = one thread per output (bit-identical)
-    long long corr_dual;           // 1: the whole-pair pipeline evaluates both directions' cost volumes in ONE launch of the fused correlation kernel (bit-identical; measured: the
-                                   //    correlation stage 0.374 -> 0.360 ms for both directions, frac 0.183 -> 0.190, but the plain argmin of the first volume then reads it from HBM instead of the Infinity
-                                   //    Cache -- 0.106 -> 0.157 ms for both -- so the pair is 0.02 ms SLOWER); 0 (default) = one launch per direction
-    long long prune_refine;        // 1 (default): a candidate box too large for one thread is closed again with the cost of the displacement nearest to the smoothed field as the
-                                   //    bound (ties at the minimum -- zero background -- otherwise keep whole windows; bit-identical); 0 = previous winner's cost only
-    long long mind_records;        // 1 (default): the whole-pair pipeline's MIND pass writes the Adam-grid pooling directly as the loop's feature records (no planar copy, no
-                                   //    k_to_chunked pass: -31 us per pair); 0 = planar pooled features + re-packing (bit-identical)
-    long long resize_up2;          // 1 (default): exact factor-2 up-sampling of a 3-channel field through k_resize_up2 (2 x 2 x 2 outputs per thread from one 27-tap
-                                   //    neighbourhood; bit-identical); 0 = one thread per output
-    long long mind_blocked;        // 1 (default): the pipeline's MIND stencil writes its raw patch SSDs blocked by the tiles of the normalise + pool pass (contiguous reads there:
-                                   //    half as many L1-miss requests for the same bytes); 0 = planar (bit-identical)
-    long long corr_cert;           // 1 (default) / 2: the whole-pair pipeline evaluates its cost volumes in the certified-fast arithmetic and takes the argmin decisions with
-                                   //    certification (certify.hip) where the geometry allows: SAME winners, SAME field bits as the exact kernels; 1 = the role kernel of
-                                   //    corrfused.hip (fast arithmetic, unscaled), 2 = the staged kernel of corrcert.hip; 0 = exact volumes
-    long long cc_debug;            // timing experiments on the certified-fast correlation kernel (bits: 1 no stores, 2 no staging after the first chunk, 4 no channel
-                                   //    sums, 8 no y pass, 16 no x / z pass): WRONG results, never set outside tools/experiments
-    long long ic_fused;            // inverse consistency: 1 = all iterations in ONE launch by 32 workgroups of one XCD with a barrier between the iterations
-                                   //    (convex.hip::k_ic_persistent; 2 = its device-side fallback forced).  MEASURED SLOWER (289 vs 145 us per call: the field accesses
-                                   //    must be agent-scope and are served behind the L2); 0 (default) = one launch per iteration (bit-identical)
-    long long mind_single;         // 1: the whole-pair pipeline's descriptor in ONE stencil pass (normalisation with the unclamped variance and both poolings inside the
-                                   //    marching kernel, k_mind_repair for the blocks where the variance clamp binds; no raw-SSD round trip: HBM traffic 7.8 x -> ~1.5 x of
-                                   //    the algorithmic bytes; bit-identical).  MEASURED SLOWER (0.546 vs 0.499 ms for both images: both forms are bound by instruction
-                                   //    issue, not by memory); 2 = every block through the repair kernel (test); 0 (default) = two passes
-    long long ms_zlen;             // planes per z chunk of the single-pass kernel (0 = automatic)
-    long long cf_map;              // fused correlation kernel, item -> workgroup order: 1 (default) = the two adjacent D-shift groups of a (dH, dW) pair in the two workgroup
-                                   //    slots of ONE CU (blocks b and b + 256 share a CU: 251 of 251 in the census), so that their moving rows meet in that CU's L1
-                                   //    (154 -> 152 us, three alternating rounds; bit-identical); 0 = large groups first
-    long long cert_unfused;        // C >= 16: the round-1 pair of kernels in the certified-fast arithmetic (correlate.hip: FMA channel chain, separable boxes without divisions)
-                                   //    1 = from K v C >= 1e9 on, 2 = whenever the geometry allows (tests), 0 (default) = never.  MEASURED: configs[3] 462 vs 503 us per
-                                   //    direction -- the raw kernel takes 290 us with either arithmetic (not issue-bound), only the boxes gain (191 -> 145 us) -- which the certified
-                                   //    passes' 0.08 ms per pair takes back
-    long long fbox_tile;           // adam_mode "fast": tile shape of the separable adjoint-box + Adam kernel (adamfast.hip): 0 = automatic, 1 = 8x10x24,
-                                   //    2 = 8x10x56, 3 = 16x10x24, 4 = 16x10x56, 5 = 8x8x32, 6 = 4x10x24 (bit-identical)
-    long long box_tile_sync;       // three-box tiles (boxtile.hip): 1 = the passes hand over through per-row readiness flags in LDS, 0 (default) = two workgroup barriers
-                                   //    (bit-identical; MEASURED SLOWER on the benchmark grid: forward tiles 16.85 vs 15.94 us)
-    long long box_prediv;          // exact Adam loop with the adjoint boxes on tiles: 1 (default) = k_warp_grad stores gU / 27 and the tiles do not divide their input taps,
-                                   //    0 = the tiles divide every tap they load (bit-identical)
-    long long tile_census_ptr;     // debugging aid: device address of a uint64 buffer of 2 x 8 x 16 x 1024 words; k_box3_tile records per wavefront the clocks of its passes
-                                   //    (boxtile.hip, tools/boxtile_census.py; 0 = off)
-};
+// ONE list, X(field = option name, environment variable or nullptr, default): struct Options, the environment defaults and the name table (api.hip) expand it.
+#define CVX_OPTIONS(X) \
+    X(mind_tiled,          "CVX_MIND_TILED",            0)  /* 1: tiled MIND stencil instead of the z-marching one */ \
+    X(mind_overlap,        "CVX_MIND_OVERLAP",          0)  /* 1: the whole-pair pipeline runs the moving image's descriptor pass on a side stream beside the fixed one's (measured: no gain) */ \
+    X(mm_tx,               "CVX_MM_TX",                 0)  /* 32 / 64: tile width of the marching MIND stencil (0 = automatic) */ \
+    X(mm_slots,            "CVX_MM_SLOTS",            512)  /* workgroup budget of the marching MIND stencil (512) */ \
+    X(box_tiled,           "CVX_BOX_TILED",             0)  /* 1: tiled three-box kernels of the Adam loop instead of the z-marching ones */ \
+    X(no_prune,            "CVX_NO_PRUNE",              0)  /* 1: streaming coupled-convex passes instead of branch and bound */ \
+    X(corr_unfused,        "CVX_CORR_UNFUSED",          0)  /* 1: k_corr_raw + k_corr_box2 instead of the fused correlation kernel */ \
+    X(corr_fused_all,      "CVX_CORR_FUSED_ALL",        0)  /* 1: the fused correlation kernel also for C >= 16 (default there: the round-1 kernels, which are faster) */ \
+    X(prune_stream_above,  "CVX_PRUNE_STREAM_ABOVE",   -1)  /* pruned pass falls back to a coalesced scan above this many 256-displacement chunks (-1 = K*v/2048) */ \
+    X(cf_census,           "CVX_CF_CENSUS",             0)  /* 1: the fused correlation kernel records per-workgroup residency in its workspace */ \
+    X(cf_prio,             "CVX_CF_PRIO",             136)  /* fused correlation kernel: issue priorities (s_setprio, 0..3) as four base-4 digits -- first-round workgroup raw / box,
+                                                                  second-round workgroup raw / box (two workgroups share a CU; 136 = 2,0,2,0: the raw stage above the boxes) */ \
+    X(warp_flat,           "CVX_WARP_FLAT",             0)  /* 1: flat 64-bit gathers in k_warp_grad instead of buffer loads */ \
+    X(box_yt,              "CVX_BOX_YT",                8)  /* rows per tile of the marching three-box kernels: 8 (default) or 4 */ \
+    X(box_wg_target,       "CVX_BOX_WG_TARGET",         0)  /* workgroups the z-marching three-box kernels of the Adam loop aim for (z-chunk length follows); 0 = automatic */ \
+    X(box_xsplit,          "CVX_BOX_XSPLIT",           -1)  /* x tiles of the marching three-box kernels: -1 automatic (rows > 62 columns: tiles of <= 56), 0 off */ \
+    X(box_cpt,             "CVX_BOX_CPT",               4)  /* output columns per thread of the marching three-box kernels: 4, or 2 (x tiles / rows <= 62 columns only) */ \
+    X(box_uneven,          "CVX_BOX_UNEVEN",          200)  /* marching three-box kernels with two workgroups per CU: length ratio (percent) of the z chunks given to the first and
+                                                                  to the second dispatch round (boxmarch.hip, BMTable); <= 100: equal chunks */ \
+    X(box_adam_role,       "CVX_BOX_ADAM_ROLE",         0)  /* adjoint + Adam kernel: 1 = the Adam update runs as a fourth role (two extra wavefronts) instead of inside every wavefront's step */ \
+    X(box_dpp,             "CVX_BOX_DPP",               0)  /* marching three-box kernels, x-tile path: 1 = halo columns through DPP lane shifts instead of a second LDS read per row */ \
+    X(box_pk,              "CVX_BOX_PK",                0)  /* marching three-box kernels: 1 = the two running sums of a column as one register pair (v_pk_add_f32 with a broadcast tap) */ \
+    X(box_prio,            "CVX_BOX_PRIO",              0)  /* marching three-box kernels: 1 / 2 = the workgroups sharing a CU alternate their issue priority step by step */ \
+    X(label_pow_block,     "CVX_LABEL_POW_BLOCK",      32)  /* cvx_label_weights_host: elements per vectorised block of the reference host's torch.pow (32: AVX-512 build, the golden host; 16: AVX2) */ \
+    X(census_ptr,          nullptr,                     0)  /* debugging aid: device address of a uint64 buffer; the Adam-loop kernels record per workgroup
+                                                                  {start, first data, end} in 100 MHz ticks (s_memrealtime) + placement there (0 = off) */ \
+    X(mind_mean_threads,   "CVX_MIND_MEAN_THREADS",     0)  /* 0: exactly rounded global mean in MINDSSC (default); T > 0: torch's own float sum with T threads
+                                                                  (reference-bits mode; NOT a bit-identical variant -- it changes the clamp bounds by ulps) */ \
+    X(edt_sequential,      "CVX_EDT_SEQUENTIAL",        0)  /* 1: squared distance transform with the sequential lower-envelope passes (one thread per line) instead of the tiled outward search */ \
+    X(warp_octant,         "CVX_WARP_OCTANT",           4)  /* adam_mode "fast" warp kernel, tile order inside an XCD's share: G >= 2 (default 4) = x fastest, then G z-adjacent tiles, then y (the tiles that share planes follow each other: FETCH_SIZE -13 %, 5.64 -> 5.59 ms per pair); 0 = plain slabs (x, y, z); 1 = one octant of the tile grid per XCD (measured: no gain) */ \
+    X(box_fwd_tile,        "CVX_BOX_FWD_TILE",         -1)  /* forward three-box pass of the Adam loop: -1 = automatic (tiles of boxtile.hip where they fill the chip), 0 = z-marching pipeline (boxmarch.hip), kind * 1000 + segments = a tile kernel variant (boxtile.hip; bit-identical) */ \
+    X(box_bwd_tile,        "CVX_BOX_BWD_TILE",         -1)  /* adjoint three-box pass (+ Adam update) of the exact Adam loop: as box_fwd_tile (-1 automatic, 0 = z-marching pipeline, kind * 1000 + segments) */ \
+    X(box_walk,            "CVX_BOX_WALK",              1)  /* 1 (default): single zero-padded box filters (sweep smoothers, final smoothing) through the z-walking kernel; 0 = one thread per output (bit-identical) */ \
+    X(corr_dual,           "CVX_CORR_DUAL",             0)  /* 1: the whole-pair pipeline evaluates both directions' cost volumes in ONE launch of the fused correlation kernel (bit-identical; measured: the
+                                                                  correlation stage 0.374 -> 0.360 ms for both directions, frac 0.183 -> 0.190, but the plain argmin of the first volume then reads it from HBM instead of the Infinity
+                                                                  Cache -- 0.106 -> 0.157 ms for both -- so the pair is 0.02 ms SLOWER); 0 (default) = one launch per direction */ \
+    X(prune_refine,        "CVX_PRUNE_REFINE",          1)  /* 1 (default): a candidate box too large for one thread is closed again with the cost of the displacement nearest to the smoothed field as the
+                                                                  bound (ties at the minimum -- zero background -- otherwise keep whole windows; bit-identical); 0 = previous winner's cost only */ \
+    X(mind_records,        "CVX_MIND_RECORDS",          1)  /* 1 (default): the whole-pair pipeline's MIND pass writes the Adam-grid pooling directly as the loop's feature records (no planar copy, no
+                                                                  k_to_chunked pass: -31 us per pair); 0 = planar pooled features + re-packing (bit-identical) */ \
+    X(resize_up2,          "CVX_RESIZE_UP2",            1)  /* 1 (default): exact factor-2 up-sampling of a 3-channel field through k_resize_up2 (2 x 2 x 2 outputs per thread from one 27-tap
+                                                                  neighbourhood; bit-identical); 0 = one thread per output */ \
+    X(mind_blocked,        "CVX_MIND_BLOCKED",          1)  /* 1 (default): the pipeline's MIND stencil writes its raw patch SSDs blocked by the tiles of the normalise + pool pass (contiguous reads there:
+                                                                  half as many L1-miss requests for the same bytes); 0 = planar (bit-identical) */ \
+    X(corr_cert,           "CVX_CORR_CERT",             1)  /* 1 (default) / 2: the whole-pair pipeline evaluates its cost volumes in the certified-fast arithmetic and takes the argmin decisions with
+                                                                  certification (certify.hip) where the geometry allows: SAME winners, SAME field bits as the exact kernels; 1 = the role kernel of
+                                                                  corrfused.hip (fast arithmetic, unscaled), 2 = the staged kernel of corrcert.hip; 0 = exact volumes */ \
+    X(cc_debug,            "CVX_CC_DEBUG",              0)  /* timing experiments on the certified-fast correlation kernel (bits: 1 no stores, 2 no staging after the first chunk, 4 no channel
+                                                                  sums, 8 no y pass, 16 no x / z pass): WRONG results, never set outside tools/experiments */ \
+    X(ic_fused,            "CVX_IC_FUSED",              0)  /* inverse consistency: 1 = all iterations in ONE launch by 32 workgroups of one XCD with a barrier between the iterations
+                                                                  (convex.hip::k_ic_persistent; 2 = its device-side fallback forced).  MEASURED SLOWER (289 vs 145 us per call: the field accesses
+                                                                  must be agent-scope and are served behind the L2); 0 (default) = one launch per iteration (bit-identical) */ \
+    X(mind_single,         "CVX_MIND_SINGLE",           0)  /* 1: the whole-pair pipeline's descriptor in ONE stencil pass (normalisation with the unclamped variance and both poolings inside the
+                                                                  marching kernel, k_mind_repair for the blocks where the variance clamp binds; no raw-SSD round trip: HBM traffic 7.8 x -> ~1.5 x of
+                                                                  the algorithmic bytes; bit-identical).  MEASURED SLOWER (0.546 vs 0.499 ms for both images: both forms are bound by instruction
+                                                                  issue, not by memory); 2 = every block through the repair kernel (test); 0 (default) = two passes */ \
+    X(ms_zlen,             "CVX_MS_ZLEN",               0)  /* planes per z chunk of the single-pass kernel (0 = automatic) */ \
+    X(cf_map,              "CVX_CF_MAP",                1)  /* fused correlation kernel, item -> workgroup order: 1 (default) = the two adjacent D-shift groups of a (dH, dW) pair in the two workgroup
+                                                                  slots of ONE CU (blocks b and b + 256 share a CU: 251 of 251 in the census), so that their moving rows meet in that CU's L1
+                                                                  (154 -> 152 us, three alternating rounds; bit-identical); 0 = large groups first */ \
+    X(cert_unfused,        "CVX_CERT_UNFUSED",          0)  /* C >= 16: the round-1 pair of kernels in the certified-fast arithmetic (correlate.hip: FMA channel chain, separable boxes without divisions)
+                                                                  1 = from K v C >= 1e9 on, 2 = whenever the geometry allows (tests), 0 (default) = never.  MEASURED: configs[3] 462 vs 503 us per
+                                                                  direction -- the raw kernel takes 290 us with either arithmetic (not issue-bound), only the boxes gain (191 -> 145 us) -- which the certified
+                                                                  passes' 0.08 ms per pair takes back */ \
+    X(fbox_tile,           "CVX_FBOX_TILE",             0)  /* adam_mode "fast": tile shape of the separable adjoint-box + Adam kernel (adamfast.hip): 0 = automatic, 1 = 8x10x24,
+                                                                  2 = 8x10x56, 3 = 16x10x24, 4 = 16x10x56, 5 = 8x8x32, 6 = 4x10x24 (bit-identical) */ \
+    X(box_tile_sync,       "CVX_BOX_TILE_SYNC",         0)  /* three-box tiles (boxtile.hip): 1 = the passes hand over through per-row readiness flags in LDS, 0 (default) = two workgroup barriers
+                                                                  (bit-identical; MEASURED SLOWER on the benchmark grid: forward tiles 16.85 vs 15.94 us) */ \
+    X(box_prediv,          "CVX_BOX_PREDIV",            1)  /* exact Adam loop with the adjoint boxes on tiles: 1 (default) = k_warp_grad stores gU / 27 and the tiles do not divide their input taps,
+                                                                  0 = the tiles divide every tap they load (bit-identical) */ \
+    X(tile_census_ptr,     nullptr,                     0)  /* debugging aid: device address of a uint64 buffer of 2 x 8 x 16 x 1024 words; k_box3_tile records per wavefront the clocks of its passes
+                                                                  (boxtile.hip, tools/boxtile_census.py; 0 = off) */
+#define X(name, env, dflt) long long name;
+struct Options { CVX_OPTIONS(X) };
+#undef X
 // All three read the context bound to the calling thread (cvx_context_bind / cvx_pair_params.ctx), else the process default context;
 // launchers copy what they need into kernel arguments at enqueue time (api.hip).
 Options& options();

@@ -287,11 +287,256 @@ static int smooth_max(const int* smooth_host, int n_smooth) {
     for (int i = 0; i < n_smooth; ++i) m = smooth_host[i] > m ? smooth_host[i] : m;
     return m;
 }
+
+// inverse-consistency tail of a convex stage (:133-141): (disp_soft / scale).flip(1) of both fields, `iters` iterations, disp_ice.flip(1) * scale * gs -> dst
+struct IcScratch { float *in1, *in2, *ic1, *ic2; void* ws; size_t ws_bytes; };
+static int ic_tail(const float* soft, const float* soft2, int h, int w, int d, int iters, const float* bh, const float* bw, const float* bd,
+                   const IcScratch& t, float gs, float* dst, hipStream_t s) {
+    const dim3 gv((unsigned)cdiv64((int64_t)h * w * d, 256));
+    hipLaunchKernelGGL(k_ic_prepare, dim3(gv.x, 2), dim3(256), 0, s, soft, soft2, h, w, d, t.in1, t.in2);
+    const int rc = cvx_inverse_consistency_f32(t.in1, t.in2, h, w, d, iters, bh, bw, bd, t.ic1, t.ic2, t.ws, t.ws_bytes, s);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_ic_finish, gv, dim3(256), 0, s, t.ic1, h, w, d, gs, dst);
+    return CVX_OK;
+}
+
+// One call of register_pair_core: what every step reads and what a step leaves for a later one; the steps are its member functions, in the order they run.
+namespace {
+struct PairRun {
+    const cvx_pair_params* p;
+    const PairLayout& L;
+    char* ws;
+    hipStream_t s;
+    const float *featF, *featM;             // full-resolution features: the caller's, or the MIND descriptors where they are written
+    bool pooled_mind = false, mind_records = false;
+    CoupledWs cw1{}, cw2{};                 // coupled-convex workspaces of the two directions (the plain argmin leaves its keys in their first key buffer)
+
+    bool no_prune() const { return options().no_prune != 0; }        // streaming coupled passes need int64 winners
+    bool f16() const { return p->fp16_storage != 0; }
+    float* F(size_t off) const { return reinterpret_cast<float*>(ws + off); }
+    int64_t* am() const { return reinterpret_cast<int64_t*>(ws + L.argmin); }
+    int64_t* am2() const { return p->ic ? reinterpret_cast<int64_t*>(ws + L.argmin2) : nullptr; }
+
+    // 1. features (:106-116), 2. coarse features (:118-119)
+    int features(const float* img_fixed, const float* img_moving) {
+        int rc;
+        // MIND path: the descriptor is consumed only through its two stride poolings, so when the window sizes tile it is never
+        // written at full resolution (launch_mind_pooled: raw patch SSDs -> normalise + exp + both poolings in one pass)
+        const bool adam = p->lambda_weight > 0;
+        pooled_mind = p->n_feat == 0 && mind_pooled_supported(p->H, p->W, p->D, p->grid_sp, adam ? p->grid_sp_adam : 0);
+        // the Adam-grid pooling of the descriptor written as the loop's feature records (no planar copy, no re-packing pass)
+        mind_records = pooled_mind && adam && options().mind_records != 0 && mind_pooled_records_supported(p->H, p->W, p->D, p->grid_sp, p->grid_sp_adam);
+        const int rec_kind = mind_records ? (p->fp16_storage ? 2 : 1) : 0;
+        if (p->n_feat == 0) {
+            const size_t mws = cvx_mindssc_workspace_bytes(p->H, p->W, p->D, p->mind_r, p->mind_d);
+            if (pooled_mind) {
+                const int g2 = adam ? p->grid_sp_adam : 0;
+                // The two images are independent until `correlate`.  Option mind_overlap = 1 runs the moving image's pass on a side stream (one
+                // image's VALU-bound stencil beside the other's memory-bound normalise + pool pass); measured on the benchmark pair: 0.52 vs
+                // 0.53 ms for the stage and a SLOWER pair (7.92 vs 7.76 ms) -- every one of these kernels fills the chip on its own -- so the
+                // default keeps them in order.
+                hipStream_t side = s; hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+                const bool overlap = options().mind_overlap != 0 && side_stream(&side, &ev_fork, &ev_join);
+                if (overlap) { (void)hipEventRecord(ev_fork, s); (void)hipStreamWaitEvent(side, ev_fork, 0); }
+                else side = s;
+                if ((rc = launch_mind_pooled(img_fixed, p->H, p->W, p->D, p->mind_r, p->mind_d, p->grid_sp, F(L.fs), g2, adam ? F(L.F2) : nullptr,
+                                             F(L.featF), ws + L.mind_ws, mws, s, rec_kind))) return rc;
+                rc = launch_mind_pooled(img_moving, p->H, p->W, p->D, p->mind_r, p->mind_d, p->grid_sp, F(L.ms), g2, adam ? F(L.M2) : nullptr,
+                                        F(L.featM), ws + (overlap ? L.mind_ws2 : L.mind_ws), mws, side, rec_kind);
+                if (overlap) { (void)hipEventRecord(ev_join, side); (void)hipStreamWaitEvent(s, ev_join, 0); }      // (joined even after an error)
+                if (rc) return rc;
+            } else {
+                if ((rc = cvx_mindssc_f32(img_fixed, p->H, p->W, p->D, p->mind_r, p->mind_d, F(L.featF), ws + L.mind_ws, mws, s))) return rc;
+                if ((rc = cvx_mindssc_f32(img_moving, p->H, p->W, p->D, p->mind_r, p->mind_d, F(L.featM), ws + L.mind_ws, mws, s))) return rc;
+            }
+            featF = F(L.featF); featM = F(L.featM);
+        }
+        mark("mind", s);
+        if (!pooled_mind) {
+            if ((rc = cvx_avgpool_f32(featF, L.C, p->H, p->W, p->D, p->grid_sp, F(L.fs), s))) return rc;
+            if ((rc = cvx_avgpool_f32(featM, L.C, p->H, p->W, p->D, p->grid_sp, F(L.ms), s))) return rc;
+        }
+        return CVX_OK;
+    }
+    // everything that depends on the geometry alone, in one launch (k_pair_setup)
+    void setup() {
+        // the plain argmin leaves its keys in the first key buffer of the coupled-convex workspace
+        Carver cv1(ws + L.conv_ws), cv2(p->ic ? ws + L.conv_ws2 : nullptr);
+        cw1 = coupled_layout(cv1, L.h, L.w, L.d, p->disp_hw); cw2 = coupled_layout(cv2, L.h, L.w, L.d, p->disp_hw);
+        const bool adam_tables = p->lambda_weight > 0;
+        // (m, v zeroed here only if 16-byte stores fit: 3 * V2 floats from a 256-byte aligned offset)
+        const bool zero_state = adam_tables && (3 * L.V2) % 4 == 0;
+        PairSetup a = {{{L.h, L.w, L.d, L.h2, L.w2, L.d2},
+                        {F(L.bh), F(L.bw), F(L.bd), adam_tables ? F(L.bh2) : nullptr, adam_tables ? F(L.bw2) : nullptr, adam_tables ? F(L.bd2) : nullptr}},
+                       p->disp_hw, F(L.mesh), {cw1.keys[0], cw2.keys[0]}, L.v,
+                       {no_prune() ? nullptr : cw1.counts, no_prune() ? nullptr : cw2.counts},
+                       {zero_state ? reinterpret_cast<float4*>(ws + L.m) : nullptr, zero_state ? reinterpret_cast<float4*>(ws + L.v_) : nullptr}, 3 * L.V2 / 4};
+        hipLaunchKernelGGL(k_pair_setup, dim3(zero_state ? 1024 : 64), dim3(256), 0, s, a);
+        if (adam_tables && !zero_state) {
+            (void)hipMemsetAsync(F(L.m), 0, sizeof(float) * 3 * L.V2, s);
+            (void)hipMemsetAsync(F(L.v_), 0, sizeof(float) * 3 * L.V2, s);
+        }
+    }
+    int plain_argmin(const float* ssd, unsigned long long* keys, int64_t* argmin, const char* done) {     // keys stay in the coupled workspace's first buffer
+        const int rc = no_prune() ? launch_argmin(ssd, f16(), nullptr, nullptr, 0.0f, false, L.K, L.v, keys, argmin, s)
+                                : launch_argmin_keys(ssd, f16(), L.K, L.v, keys, /*arm=*/false, s);
+        if (rc == CVX_OK) mark(done, s);
+        return rc;
+    }
+    // one direction of the exact convex stage: cost volume, plain argmin, a profile mark behind each
+    int exact_direction(const float* fix, const float* mov, const cvx_corr_opts* copt, float* ssd, unsigned long long* keys, int64_t* argmin,
+                        const char* correlated, const char* done) {
+        const int rc = cvx_correlate_ex_f32(fix, mov, L.C, L.h, L.w, L.d, p->disp_hw, copt, ssd, nullptr, ws + L.corr_ws,
+                                            cvx_correlate_workspace_bytes(L.C, L.h, L.w, L.d, p->disp_hw), s);
+        if (rc) return rc;
+        mark(correlated, s);
+        return plain_argmin(ssd, keys, argmin, done);
+    }
+    // 3. forward (and reverse) correlation + coupled convex                      (:124-130)
+    int convex() {
+        int rc;
+        const cvx_corr_opts copt = {p->cost, p->n_box == 1 ? 1 : 2, p->corr_fast, f16() ? 2 : 0};
+        const bool variant = copt.cost || copt.n_box == 1 || copt.fast || copt.f16;
+        if (p->fp16_storage) {                      // features are stored in half precision by the reference's GPU default (MIND:79)
+            if ((rc = cvx_round_f16_f32(F(L.fs), (int64_t)L.C * L.v, s)) || (rc = cvx_round_f16_f32(F(L.ms), (int64_t)L.C * L.v, s))) return rc;
+        }
+        // Certified-fast path (option corr_cert, default): the cost volumes in the fast arithmetic (unscaled, 2^-16 relative to ATen's), every
+        // argmin decision certified against the exact arithmetic or evaluated exactly (certify.hip) -- the SAME winners, hence the same field bits,
+        // as the exact kernels below; packaged operator only (SSD, two boxes, float32, pruned passes).
+        // (C >= 16: the role kernel carries the channel sums in a third of its wavefronts.  In the fast arithmetic it needs no cascade -- 64 registers, two
+        // workgroups per CU -- and beats the exact kernels up to 32 channels where its items fill the chip: C = 32 at 26x32x37 hw 6 0.36 vs 0.45 ms,
+        // C = 16 0.21 vs 0.33; with 162 items (hw 4) or 64 channels it loses -- C = 64 hw 4: 0.56 vs 0.23 ms --, tools/experiments/corr_time_c.py;
+        // corr_cert = 2 keeps the staged kernel selectable for every supported C)
+        const bool cert = options().corr_cert != 0 && !variant && !no_prune() && corr_certfast_supported(L.C, L.h, L.w, L.d, p->disp_hw) &&
+                          (options().corr_cert == 2 || corr_certfast_pays(L.C, L.h, L.w, L.d, p->disp_hw));
+        if (cert) {
+            const size_t fws = corr_certfast_workspace_bytes(L.C, L.h, L.w, L.d, p->disp_hw), qws = corr_certify_workspace_bytes(L.C, L.h, L.w, L.d, p->disp_hw);
+            auto cert_stage = [&](int stage) {
+                return coupled_convex_cert_impl(F(L.ssd), F(L.fs), F(L.ms), F(L.soft), ws + L.cert_ws, p->ic ? F(L.ssd2) : nullptr, F(L.ms), F(L.fs),
+                                                p->ic ? F(L.soft2) : nullptr, p->ic ? ws + L.cert_ws2 : nullptr, F(L.mesh), L.C, L.h, L.w, L.d, p->disp_hw, qws, s, stage);
+            };
+            if ((rc = cert_stage(1))) return rc;                                    // keys, counters, tail values
+            if ((rc = launch_corr_certfast(F(L.fs), F(L.ms), L.C, L.h, L.w, L.d, p->disp_hw, F(L.ssd), ws + L.corr_ws, fws, s))) return rc;
+            mark("correlate", s);
+            if ((rc = cert_stage(2))) return rc;                                    // the plain argmin streams the volume while the Infinity Cache holds it
+            mark("argmin", s);
+            if (p->ic) {
+                if ((rc = launch_corr_certfast(F(L.ms), F(L.fs), L.C, L.h, L.w, L.d, p->disp_hw, F(L.ssd2), ws + L.corr_ws, fws, s))) return rc;
+                mark("correlate_rev", s);
+                if ((rc = cert_stage(3))) return rc;
+                mark("argmin_rev", s);
+            }
+            if ((rc = cert_stage(4))) return rc;
+            return cert_stage(5);
+        }
+        // Both directions' cost volumes in ONE launch of the fused kernel when the pair is inverse consistent (option corr_dual): the stage
+        // interval "correlate" then covers both directions and "correlate_rev" is not recorded.
+        const bool dual = p->ic && options().corr_dual != 0 && !corr_use_unfused(L.C, L.h, L.w, L.d, p->disp_hw, variant) && p->disp_hw <= CVX_MAX_DISP_HW;
+        if (dual) {
+            const size_t fws = corr_fused_workspace_bytes(L.C, L.h, L.w, L.d, p->disp_hw);
+            if ((rc = launch_corr_fused_dual(F(L.fs), F(L.ms), L.C, L.h, L.w, L.d, p->disp_hw, copt.cost, copt.n_box, copt.fast, copt.f16, F(L.ssd), F(L.ssd2),
+                                             ws + L.corr_ws, fws, ws + L.corr_ws2, s))) return rc;
+            mark("correlate", s);
+            if ((rc = plain_argmin(F(L.ssd), cw1.keys[0], am(), "argmin"))) return rc;
+            if ((rc = plain_argmin(F(L.ssd2), cw2.keys[0], am2(), "argmin_rev"))) return rc;
+        } else {
+            if ((rc = exact_direction(F(L.fs), F(L.ms), variant ? &copt : nullptr, F(L.ssd), cw1.keys[0], am(), "correlate", "argmin"))) return rc;
+            // reverse direction (:136-138): same operators with the roles swapped
+            if (p->ic && (rc = exact_direction(F(L.ms), F(L.fs), variant ? &copt : nullptr, F(L.ssd2), cw2.keys[0], am2(), "correlate_rev", "argmin_rev"))) return rc;
+        }
+        // both coupled-convex solves in the same launches (ic) or the forward one alone
+        return coupled_convex_dual_impl(F(L.ssd), no_prune() ? am() : nullptr, F(L.soft), ws + L.conv_ws, p->ic ? F(L.ssd2) : nullptr, f16(), no_prune() ? am2() : nullptr,
+                                        p->ic ? F(L.soft2) : nullptr, p->ic ? ws + L.conv_ws2 : nullptr, F(L.mesh), L.h, L.w, L.d,
+                                        p->disp_hw, cvx_coupled_convex_workspace_bytes(L.h, L.w, L.d, p->disp_hw), s, /*counts_zeroed=*/!no_prune());
+    }
+    // dst = interpolate(src * grid_sp_adam, (H,W,D)) of an Adam-grid field (:182), then k > 0: three zero-padded k^3 box filters (:185-191)
+    int upsample_smoothed(const float* src, int k, float* dst) {
+        int rc;
+        if (k <= 0) return launch_resize(src, 3, L.h2, L.w2, L.d2, dst, p->H, p->W, p->D, (float)p->grid_sp_adam, 1.0f, s);
+        float *tmp = F(L.smooth_ws), *tmp2 = F(L.smooth_ws2);
+        if ((rc = launch_resize(src, 3, L.h2, L.w2, L.d2, tmp, p->H, p->W, p->D, (float)p->grid_sp_adam, 1.0f, s))) return rc;
+        if ((rc = launch_box_zero(tmp, tmp2, 3, p->H, p->W, p->D, k, false, s))) return rc;
+        if ((rc = launch_box_zero(tmp2, tmp, 3, p->H, p->W, p->D, k, false, s))) return rc;
+        return launch_box_zero(tmp, dst, 3, p->H, p->W, p->D, k, false, s);
+    }
+    // Adam instance optimisation and the full-resolution output                   (:147-191)
+    int adam_and_output(const int* snap_iters_host, int n_snap, const int* smooth_host, int n_smooth, float* out_field) {
+        int rc;
+        if (!pooled_mind) {
+            if ((rc = cvx_avgpool_f32(featF, L.C, p->H, p->W, p->D, p->grid_sp_adam, F(L.F2), s))) return rc;
+            if ((rc = cvx_avgpool_f32(featM, L.C, p->H, p->W, p->D, p->grid_sp_adam, F(L.M2), s))) return rc;
+        }
+        // disp_lr = interpolate(disp_hr, (H2,W2,D2)); weight = disp_lr / grid_sp_adam       (:153,156)
+        // ic=True: the up-sampling of the coarse field (L.upin) is folded into this resize; ic=False: coarse field, coarse units (:143-144)
+        if (p->ic) rc = launch_resize2(F(L.upin), 3, L.h, L.w, L.d, p->H, p->W, p->D, F(L.disp_hr), F(L.P), L.h2, L.w2, L.d2, (float)p->grid_sp_adam, s);
+        else rc = launch_resize(F(L.soft), 3, L.h, L.w, L.d, F(L.P), L.h2, L.w2, L.d2, 1.0f, (float)p->grid_sp_adam, s);
+        if (rc) return rc;
+        // (m = v = 0: k_pair_setup)
+        // (fp16 storage: the Adam loop keeps its feature records in half precision -- rounded when the records are built)
+        mark("adam_setup", s);
+        const cvx_smoother two_pools = {0, 2, {3, 3, 0, 0}, {0.f, 0.f, 0.f, 0.f, 0.f}};            // task3_docker.py:191
+        if ((rc = adam_run_impl(F(L.F2), F(L.M2), L.C, L.h2, L.w2, L.d2, F(L.P), F(L.m), F(L.v_), p->lambda_weight,
+                                p->selected_niter, 0, p->cost_scale, F(L.bh2), F(L.bw2), F(L.bd2), F(L.U), nullptr, snap_iters_host, n_snap,
+                                n_snap ? F(L.snaps) : nullptr, p->n_spline_pools == 2 ? &two_pools : nullptr, /*keep_state=*/false, f16(), p->adam_fast, ws + L.adam_ws,
+                                cvx_adam_workspace_bytes(L.C, L.h2, L.w2, L.d2), s, mind_records))) return rc;
+        mark("adam", s);
+        // disp_hr = interpolate(fitted_grid * grid_sp_adam, (H,W,D))                            (:182)
+        if (n_snap > 0) {                       // self_configuring/convex_adam_MIND.py:115-139: every snapshot x every final smoothing
+            for (int i = 0; i < n_snap; ++i)
+                for (int j = 0; j < n_smooth; ++j)
+                    if ((rc = upsample_smoothed(F(L.snaps) + (size_t)i * 3 * L.V2, smooth_host[j], out_field + ((size_t)i * n_smooth + j) * 3 * L.V))) return rc;
+        } else if ((rc = upsample_smoothed(F(L.U), p->selected_smooth, out_field))) return rc;
+        mark("upsample", s);
+        return CVX_OK;
+    }
+};
+}  // namespace
+
 // out_field: the field of the packaged pipeline ([3][H][W][D]) when n_snap == 0; otherwise [n_snap][n_smooth][3][H][W][D]: for every
 // listed Adam iteration the up-sampled disp_sample of that iteration, once per listed final smoothing (0 = none, k = three k^3 boxes)
 static int register_pair_core(const float* img_fixed, const float* img_moving, const float* feat_fixed, const float* feat_moving,
                               const cvx_pair_params* p, float* out_field, int* out_dims_host, const int* snap_iters_host, int n_snap,
-                              const int* smooth_host, int n_smooth, void* workspace, size_t workspace_bytes, void* stream);
+                              const int* smooth_host, int n_smooth, void* workspace, size_t workspace_bytes, void* stream) {
+    int rc = validate(p);
+    if (rc) return rc;
+    const ContextScope scope(p->ctx);           // switches and tables of this call (cvx_pair_params.ctx; nullptr keeps the thread's)
+    CVX_REQUIRE(out_field && workspace, "cvx_register_pair_f32: null pointer");
+    if (p->n_feat == 0) CVX_REQUIRE(img_fixed && img_moving, "cvx_register_pair_f32: images missing");
+    else CVX_REQUIRE(feat_fixed && feat_moving, "cvx_register_pair_f32: feature volumes missing");
+    const PairLayout L = pair_layout(*p, n_snap, n_snap ? smooth_max(smooth_host, n_smooth) : 0);
+    if (workspace_bytes < L.total) return fail(CVX_ERR_WORKSPACE, "cvx_register_pair_f32: workspace %zu < %zu", workspace_bytes, L.total);
+    hipStream_t s = as_stream(stream);
+    if (g_profiling < 2) { g_marks.clear(); g_pool_used = 0; }
+    mark("start", s);
+    // stage intervals "correlate" / "correlate_rev" = the fused kernel alone; the padded feature copies (and the certification set-up before them) are
+    // "correlate_prep" (only while profiling: the hook records an event)
+    corr_fused_set_prep_hook(g_profiling ? +[](hipStream_t st) { mark("correlate_prep", st); } : nullptr);
+    struct HookReset { ~HookReset() { corr_fused_set_prep_hook(nullptr); } } hook_reset;
+
+    PairRun run = {p, L, static_cast<char*>(workspace), s, feat_fixed, feat_moving};
+    const bool adam = p->lambda_weight > 0;
+    if ((rc = run.features(img_fixed, img_moving))) return rc;
+    run.setup();
+    mark("pool", s);
+    if ((rc = run.convex())) return rc;
+    mark("coupled_convex", s);
+    if (p->ic) {                                // (:133-141)
+        const IcScratch t = {run.F(L.in1), run.F(L.in2), run.F(L.ic1), run.F(L.ic2), run.ws + L.ic_ws, cvx_inverse_consistency_workspace_bytes(L.h, L.w, L.d)};
+        if ((rc = ic_tail(run.F(L.soft), run.F(L.soft2), L.h, L.w, L.d, 15, run.F(L.bh), run.F(L.bw), run.F(L.bd), t, (float)p->grid_sp, run.F(L.upin), s))) return rc;
+        // with the Adam stage following, disp_hr is only ever read by the down-sampling to the Adam grid: the two resizes are
+        // folded into one there (launch_resize2) and the full-resolution field is never written
+        if (!adam && (rc = launch_resize(run.F(L.upin), 3, L.h, L.w, L.d, out_field, p->H, p->W, p->D, 1.0f, 1.0f, s))) return rc;
+        mark("inverse_consistency", s);
+    }
+    if (adam) {
+        if ((rc = run.adam_and_output(snap_iters_host, n_snap, smooth_host, n_smooth, out_field))) return rc;
+    } else if (!p->ic) {                        // ic=False: coarse field, coarse units (:143-144)
+        (void)hipMemcpyAsync(out_field, run.F(L.soft), sizeof(float) * 3 * L.v, hipMemcpyDeviceToDevice, s);
+    }
+    const bool full = p->ic || adam;
+    if (out_dims_host) { out_dims_host[0] = full ? p->H : L.h; out_dims_host[1] = full ? p->W : L.w; out_dims_host[2] = full ? p->D : L.d; }
+    return check_last("register_pair");
+}
 }  // namespace cvx
 
 extern "C" int cvx_register_pair_f32(const float* img_fixed, const float* img_moving, const float* feat_fixed,
@@ -323,239 +568,6 @@ extern "C" int cvx_register_pair_snapshots_f32(const float* img_fixed, const flo
     return register_pair_core(img_fixed, img_moving, feat_fixed, feat_moving, p, out_fields, nullptr, snapshot_iters_host, n_snap, smooth_host,
                               n_smooth, workspace, workspace_bytes, stream);
 }
-
-static int cvx::register_pair_core(const float* img_fixed, const float* img_moving, const float* feat_fixed, const float* feat_moving,
-                                   const cvx_pair_params* p, float* out_field, int* out_dims_host, const int* snap_iters_host, int n_snap,
-                                   const int* smooth_host, int n_smooth, void* workspace, size_t workspace_bytes, void* stream) {
-    int rc = validate(p);
-    if (rc) return rc;
-    const ContextScope scope(p->ctx);           // switches and tables of this call (cvx_pair_params.ctx; nullptr keeps the thread's)
-    CVX_REQUIRE(out_field && workspace, "cvx_register_pair_f32: null pointer");
-    if (p->n_feat == 0) CVX_REQUIRE(img_fixed && img_moving, "cvx_register_pair_f32: images missing");
-    else CVX_REQUIRE(feat_fixed && feat_moving, "cvx_register_pair_f32: feature volumes missing");
-    const PairLayout L = pair_layout(*p, n_snap, n_snap ? smooth_max(smooth_host, n_smooth) : 0);
-    if (workspace_bytes < L.total) return fail(CVX_ERR_WORKSPACE, "cvx_register_pair_f32: workspace %zu < %zu", workspace_bytes, L.total);
-    hipStream_t s = as_stream(stream);
-    char* ws = static_cast<char*>(workspace);
-    auto F = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
-    if (g_profiling < 2) { g_marks.clear(); g_pool_used = 0; }
-    mark("start", s);
-    // stage intervals "correlate" / "correlate_rev" = the fused kernel alone; the padded feature copies (and the certification set-up before them) are
-    // "correlate_prep" (only while profiling: the hook records an event)
-    corr_fused_set_prep_hook(g_profiling ? +[](hipStream_t st) { mark("correlate_prep", st); } : nullptr);
-    struct HookReset { ~HookReset() { corr_fused_set_prep_hook(nullptr); } } hook_reset;
-
-    // 1. features                                                              (:106-116)
-    const float *featF = feat_fixed, *featM = feat_moving;
-    // MIND path: the descriptor is consumed only through its two stride poolings, so when the window sizes tile it is never
-    // written at full resolution (launch_mind_pooled: raw patch SSDs -> normalise + exp + both poolings in one pass)
-    const bool adam = p->lambda_weight > 0;
-    const bool pooled_mind = p->n_feat == 0 && mind_pooled_supported(p->H, p->W, p->D, p->grid_sp, adam ? p->grid_sp_adam : 0);
-    // the Adam-grid pooling of the descriptor written as the loop's feature records (no planar copy, no re-packing pass)
-    const bool mind_records = pooled_mind && adam && options().mind_records != 0 && mind_pooled_records_supported(p->H, p->W, p->D, p->grid_sp, p->grid_sp_adam);
-    const int rec_kind = mind_records ? (p->fp16_storage ? 2 : 1) : 0;
-    if (p->n_feat == 0) {
-        const size_t mws = cvx_mindssc_workspace_bytes(p->H, p->W, p->D, p->mind_r, p->mind_d);
-        if (pooled_mind) {
-            const int g2 = adam ? p->grid_sp_adam : 0;
-            // The two images are independent until `correlate`.  Option mind_overlap = 1 runs the moving image's pass on a side stream (one
-            // image's VALU-bound stencil beside the other's memory-bound normalise + pool pass); measured on the benchmark pair: 0.52 vs
-            // 0.53 ms for the stage and a SLOWER pair (7.92 vs 7.76 ms) -- every one of these kernels fills the chip on its own -- so the
-            // default keeps them in order.
-            hipStream_t side = s; hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-            const bool overlap = options().mind_overlap != 0 && side_stream(&side, &ev_fork, &ev_join);
-            if (overlap) { (void)hipEventRecord(ev_fork, s); (void)hipStreamWaitEvent(side, ev_fork, 0); }
-            else side = s;
-            if ((rc = launch_mind_pooled(img_fixed, p->H, p->W, p->D, p->mind_r, p->mind_d, p->grid_sp, F(L.fs), g2, adam ? F(L.F2) : nullptr,
-                                         F(L.featF), ws + L.mind_ws, mws, s, rec_kind))) return rc;
-            rc = launch_mind_pooled(img_moving, p->H, p->W, p->D, p->mind_r, p->mind_d, p->grid_sp, F(L.ms), g2, adam ? F(L.M2) : nullptr,
-                                    F(L.featM), ws + (overlap ? L.mind_ws2 : L.mind_ws), mws, side, rec_kind);
-            if (overlap) { (void)hipEventRecord(ev_join, side); (void)hipStreamWaitEvent(s, ev_join, 0); }      // (joined even after an error)
-            if (rc) return rc;
-        } else {
-            if ((rc = cvx_mindssc_f32(img_fixed, p->H, p->W, p->D, p->mind_r, p->mind_d, F(L.featF), ws + L.mind_ws, mws, stream))) return rc;
-            if ((rc = cvx_mindssc_f32(img_moving, p->H, p->W, p->D, p->mind_r, p->mind_d, F(L.featM), ws + L.mind_ws, mws, stream))) return rc;
-        }
-        featF = F(L.featF); featM = F(L.featM);
-    }
-    mark("mind", s);
-    // 2. coarse features                                                       (:118-119)
-    if (!pooled_mind) {
-        if ((rc = cvx_avgpool_f32(featF, L.C, p->H, p->W, p->D, p->grid_sp, F(L.fs), stream))) return rc;
-        if ((rc = cvx_avgpool_f32(featM, L.C, p->H, p->W, p->D, p->grid_sp, F(L.ms), stream))) return rc;
-    }
-    const size_t vws = cvx_coupled_convex_workspace_bytes(L.h, L.w, L.d, p->disp_hw);
-    // the plain argmin leaves its keys in the first key buffer of the coupled-convex workspace
-    Carver cv1(ws + L.conv_ws), cv2(p->ic ? ws + L.conv_ws2 : nullptr);
-    const CoupledWs cw1 = coupled_layout(cv1, L.h, L.w, L.d, p->disp_hw), cw2 = coupled_layout(cv2, L.h, L.w, L.d, p->disp_hw);
-    unsigned long long *keys = cw1.keys[0], *keys2 = cw2.keys[0];
-    const bool no_prune = options().no_prune != 0;        // streaming coupled passes need int64 winners
-    {
-        const bool adam_tables = p->lambda_weight > 0;
-        // (m, v zeroed here only if 16-byte stores fit: 3 * V2 floats from a 256-byte aligned offset)
-        const bool zero_state = adam_tables && (3 * L.V2) % 4 == 0;
-        PairSetup a = {{{L.h, L.w, L.d, L.h2, L.w2, L.d2},
-                        {F(L.bh), F(L.bw), F(L.bd), adam_tables ? F(L.bh2) : nullptr, adam_tables ? F(L.bw2) : nullptr, adam_tables ? F(L.bd2) : nullptr}},
-                       p->disp_hw, F(L.mesh), {keys, keys2}, L.v,
-                       {no_prune ? nullptr : cw1.counts, no_prune ? nullptr : cw2.counts},
-                       {zero_state ? reinterpret_cast<float4*>(ws + L.m) : nullptr, zero_state ? reinterpret_cast<float4*>(ws + L.v_) : nullptr}, 3 * L.V2 / 4};
-        hipLaunchKernelGGL(k_pair_setup, dim3(zero_state ? 1024 : 64), dim3(256), 0, s, a);
-        if (adam_tables && !zero_state) {
-            (void)hipMemsetAsync(F(L.m), 0, sizeof(float) * 3 * L.V2, s);
-            (void)hipMemsetAsync(F(L.v_), 0, sizeof(float) * 3 * L.V2, s);
-        }
-    }
-    mark("pool", s);
-    // 3. forward correlation + coupled convex                                  (:124-130)
-    const size_t cws = cvx_correlate_workspace_bytes(L.C, L.h, L.w, L.d, p->disp_hw);
-    int64_t* am = reinterpret_cast<int64_t*>(ws + L.argmin);
-    const bool f16 = p->fp16_storage != 0;
-    const cvx_corr_opts copt = {p->cost, p->n_box == 1 ? 1 : 2, p->corr_fast, f16 ? 2 : 0};
-    const bool variant = copt.cost || copt.n_box == 1 || copt.fast || copt.f16;
-    if (p->fp16_storage) {                      // features are stored in half precision by the reference's GPU default (MIND:79)
-        if ((rc = cvx_round_f16_f32(F(L.fs), (int64_t)L.C * L.v, stream)) || (rc = cvx_round_f16_f32(F(L.ms), (int64_t)L.C * L.v, stream))) return rc;
-    }
-    // Certified-fast path (option corr_cert, default): the cost volumes in the fast arithmetic (unscaled, 2^-16 relative to ATen's), every
-    // argmin decision certified against the exact arithmetic or evaluated exactly (certify.hip) -- the SAME winners, hence the same field bits,
-    // as the exact kernels below; packaged operator only (SSD, two boxes, float32, pruned passes).
-    // (C >= 16: the role kernel carries the channel sums in a third of its wavefronts.  In the fast arithmetic it needs no cascade -- 64 registers, two
-    // workgroups per CU -- and beats the exact kernels up to 32 channels where its items fill the chip: C = 32 at 26x32x37 hw 6 0.36 vs 0.45 ms,
-    // C = 16 0.21 vs 0.33; with 162 items (hw 4) or 64 channels it loses -- C = 64 hw 4: 0.56 vs 0.23 ms --, tools/experiments/corr_time_c.py;
-    // corr_cert = 2 keeps the staged kernel selectable for every supported C)
-    const bool cert = options().corr_cert != 0 && !variant && !no_prune && corr_certfast_supported(L.C, L.h, L.w, L.d, p->disp_hw) &&
-                      (options().corr_cert == 2 || corr_certfast_pays(L.C, L.h, L.w, L.d, p->disp_hw));
-    int64_t* am2 = p->ic ? reinterpret_cast<int64_t*>(ws + L.argmin2) : nullptr;
-    if (cert) {
-        const size_t fws = corr_certfast_workspace_bytes(L.C, L.h, L.w, L.d, p->disp_hw), qws = corr_certify_workspace_bytes(L.C, L.h, L.w, L.d, p->disp_hw);
-        auto cert_stage = [&](int stage) {
-            return coupled_convex_cert_impl(F(L.ssd), F(L.fs), F(L.ms), F(L.soft), ws + L.cert_ws, p->ic ? F(L.ssd2) : nullptr, F(L.ms), F(L.fs),
-                                            p->ic ? F(L.soft2) : nullptr, p->ic ? ws + L.cert_ws2 : nullptr, F(L.mesh), L.C, L.h, L.w, L.d, p->disp_hw, qws, s, stage);
-        };
-        if ((rc = cert_stage(1))) return rc;                                    // keys, counters, tail values
-        if ((rc = launch_corr_certfast(F(L.fs), F(L.ms), L.C, L.h, L.w, L.d, p->disp_hw, F(L.ssd), ws + L.corr_ws, fws, s))) return rc;
-        mark("correlate", s);
-        if ((rc = cert_stage(2))) return rc;                                    // the plain argmin streams the volume while the Infinity Cache holds it
-        mark("argmin", s);
-        if (p->ic) {
-            if ((rc = launch_corr_certfast(F(L.ms), F(L.fs), L.C, L.h, L.w, L.d, p->disp_hw, F(L.ssd2), ws + L.corr_ws, fws, s))) return rc;
-            mark("correlate_rev", s);
-            if ((rc = cert_stage(3))) return rc;
-            mark("argmin_rev", s);
-        }
-        if ((rc = cert_stage(4)) || (rc = cert_stage(5))) return rc;
-    } else {
-    // Both directions' cost volumes in ONE launch of the fused kernel when the pair is inverse consistent (option corr_dual): the stage
-    // interval "correlate" then covers both directions and "correlate_rev" is not recorded.
-    const bool dual = p->ic && options().corr_dual != 0 && !corr_use_unfused(L.C, L.h, L.w, L.d, p->disp_hw, variant) && p->disp_hw <= CVX_MAX_DISP_HW;
-    if (dual) {
-        const size_t fws = corr_fused_workspace_bytes(L.C, L.h, L.w, L.d, p->disp_hw);
-        if ((rc = launch_corr_fused_dual(F(L.fs), F(L.ms), L.C, L.h, L.w, L.d, p->disp_hw, copt.cost, copt.n_box, copt.fast, copt.f16, F(L.ssd), F(L.ssd2),
-                                         ws + L.corr_ws, fws, ws + L.corr_ws2, s))) return rc;
-        mark("correlate", s);
-        if (no_prune) rc = launch_argmin(F(L.ssd), f16, nullptr, nullptr, 0.0f, false, L.K, L.v, keys, am, s);
-        else rc = launch_argmin_keys(F(L.ssd), f16, L.K, L.v, keys, /*arm=*/false, s);
-        if (rc) return rc;
-        mark("argmin", s);
-        if (no_prune) rc = launch_argmin(F(L.ssd2), f16, nullptr, nullptr, 0.0f, false, L.K, L.v, keys2, am2, s);
-        else rc = launch_argmin_keys(F(L.ssd2), f16, L.K, L.v, keys2, /*arm=*/false, s);
-        if (rc) return rc;
-        mark("argmin_rev", s);
-    } else {
-    if ((rc = cvx_correlate_ex_f32(F(L.fs), F(L.ms), L.C, L.h, L.w, L.d, p->disp_hw, variant ? &copt : nullptr, F(L.ssd), nullptr, ws + L.corr_ws, cws, stream))) return rc;
-    mark("correlate", s);
-    if (no_prune) rc = launch_argmin(F(L.ssd), f16, nullptr, nullptr, 0.0f, false, L.K, L.v, keys, am, s);
-    else rc = launch_argmin_keys(F(L.ssd), f16, L.K, L.v, keys, /*arm=*/false, s);            // keys stay in the coupled workspace's first buffer
-    if (rc) return rc;
-    mark("argmin", s);
-    if (p->ic) {                                // reverse direction (:136-138): same operators with the roles swapped
-        if ((rc = cvx_correlate_ex_f32(F(L.ms), F(L.fs), L.C, L.h, L.w, L.d, p->disp_hw, variant ? &copt : nullptr, F(L.ssd2), nullptr, ws + L.corr_ws, cws, stream))) return rc;
-        mark("correlate_rev", s);
-        if (no_prune) rc = launch_argmin(F(L.ssd2), f16, nullptr, nullptr, 0.0f, false, L.K, L.v, keys2, am2, s);
-        else rc = launch_argmin_keys(F(L.ssd2), f16, L.K, L.v, keys2, /*arm=*/false, s);
-        if (rc) return rc;
-        mark("argmin_rev", s);
-    }
-    }
-    // both coupled-convex solves in the same launches (ic) or the forward one alone
-    if ((rc = coupled_convex_dual_impl(F(L.ssd), no_prune ? am : nullptr, F(L.soft), ws + L.conv_ws, p->ic ? F(L.ssd2) : nullptr, f16, no_prune ? am2 : nullptr,
-                                       p->ic ? F(L.soft2) : nullptr, p->ic ? ws + L.conv_ws2 : nullptr, F(L.mesh), L.h, L.w, L.d,
-                                       p->disp_hw, vws, stream, /*counts_zeroed=*/!no_prune))) return rc;
-    }
-    mark("coupled_convex", s);
-
-    const float* disp_hr = F(L.soft);          // ic=False: coarse field, coarse units (:143-144)
-    const float* coarse_src = nullptr;         // ic=True + Adam: the coarse field whose up-sampling is folded into the next resize
-    int hh = L.h, hw_ = L.w, hd = L.d;
-    if (p->ic) {                                // (:133-141)
-        const dim3 gv((unsigned)cdiv64((int64_t)L.v, 256));
-        hipLaunchKernelGGL(k_ic_prepare, dim3(gv.x, 2), dim3(256), 0, s, F(L.soft), F(L.soft2), L.h, L.w, L.d, F(L.in1), F(L.in2));
-        if ((rc = cvx_inverse_consistency_f32(F(L.in1), F(L.in2), L.h, L.w, L.d, 15, F(L.bh), F(L.bw), F(L.bd), F(L.ic1), F(L.ic2),
-                                              ws + L.ic_ws, cvx_inverse_consistency_workspace_bytes(L.h, L.w, L.d), stream))) return rc;
-        hipLaunchKernelGGL(k_ic_finish, gv, dim3(256), 0, s, F(L.ic1), L.h, L.w, L.d, (float)p->grid_sp, F(L.upin));
-        // with the Adam stage following, disp_hr is only ever read by the down-sampling to the Adam grid: the two resizes are
-        // folded into one there (launch_resize2) and the full-resolution field is never written
-        if (p->lambda_weight > 0) { coarse_src = F(L.upin); }
-        else {
-            if ((rc = launch_resize(F(L.upin), 3, L.h, L.w, L.d, out_field, p->H, p->W, p->D, 1.0f, 1.0f, s))) return rc;
-            disp_hr = out_field;
-        }
-        hh = p->H; hw_ = p->W; hd = p->D;
-        mark("inverse_consistency", s);
-    }
-
-    if (p->lambda_weight > 0) {                 // (:147-191)
-        if (!pooled_mind) {
-            if ((rc = cvx_avgpool_f32(featF, L.C, p->H, p->W, p->D, p->grid_sp_adam, F(L.F2), stream))) return rc;
-            if ((rc = cvx_avgpool_f32(featM, L.C, p->H, p->W, p->D, p->grid_sp_adam, F(L.M2), stream))) return rc;
-        }
-        // disp_lr = interpolate(disp_hr, (H2,W2,D2)); weight = disp_lr / grid_sp_adam       (:153,156)
-        if (coarse_src) {
-            if ((rc = launch_resize2(coarse_src, 3, L.h, L.w, L.d, hh, hw_, hd, F(L.disp_hr), F(L.P), L.h2, L.w2, L.d2, (float)p->grid_sp_adam, s))) return rc;
-        } else if ((rc = launch_resize(disp_hr, 3, hh, hw_, hd, F(L.P), L.h2, L.w2, L.d2, 1.0f, (float)p->grid_sp_adam, s))) return rc;
-        // (m = v = 0: k_pair_setup)
-        // (fp16 storage: the Adam loop keeps its feature records in half precision -- rounded when the records are built)
-        mark("adam_setup", s);
-        const cvx_smoother two_pools = {0, 2, {3, 3, 0, 0}, {0.f, 0.f, 0.f, 0.f, 0.f}};            // task3_docker.py:191
-        if ((rc = adam_run_impl(F(L.F2), F(L.M2), L.C, L.h2, L.w2, L.d2, F(L.P), F(L.m), F(L.v_), p->lambda_weight,
-                                p->selected_niter, 0, p->cost_scale, F(L.bh2), F(L.bw2), F(L.bd2), F(L.U), nullptr, snap_iters_host, n_snap,
-                                n_snap ? F(L.snaps) : nullptr, p->n_spline_pools == 2 ? &two_pools : nullptr, /*keep_state=*/false, f16, p->adam_fast, ws + L.adam_ws,
-                                cvx_adam_workspace_bytes(L.C, L.h2, L.w2, L.d2), stream, mind_records))) return rc;
-        mark("adam", s);
-        // disp_hr = interpolate(fitted_grid * grid_sp_adam, (H,W,D))                            (:182)
-        if (n_snap > 0) {                       // self_configuring/convex_adam_MIND.py:115-139: every snapshot x every final smoothing
-            float* tmp = F(L.smooth_ws);
-            float* tmp2 = L.smooth_ws ? F(L.smooth_ws2) : nullptr;
-            for (int i = 0; i < n_snap; ++i)
-                for (int j = 0; j < n_smooth; ++j) {
-                    float* dst = out_field + ((size_t)i * n_smooth + j) * 3 * L.V;
-                    const float* snap = F(L.snaps) + (size_t)i * 3 * L.V2;
-                    const int k = smooth_host[j];
-                    if (k > 0) {
-                        if ((rc = launch_resize(snap, 3, L.h2, L.w2, L.d2, tmp, p->H, p->W, p->D, (float)p->grid_sp_adam, 1.0f, s))) return rc;
-                        if ((rc = launch_box_zero(tmp, tmp2, 3, p->H, p->W, p->D, k, false, s))) return rc;
-                        if ((rc = launch_box_zero(tmp2, tmp, 3, p->H, p->W, p->D, k, false, s))) return rc;
-                        if ((rc = launch_box_zero(tmp, dst, 3, p->H, p->W, p->D, k, false, s))) return rc;
-                    } else if ((rc = launch_resize(snap, 3, L.h2, L.w2, L.d2, dst, p->H, p->W, p->D, (float)p->grid_sp_adam, 1.0f, s))) return rc;
-                }
-        } else if (p->selected_smooth > 0) {
-            float* tmp = F(L.smooth_ws);
-            float* tmp2 = F(L.smooth_ws2);
-            if ((rc = launch_resize(F(L.U), 3, L.h2, L.w2, L.d2, tmp, p->H, p->W, p->D, (float)p->grid_sp_adam, 1.0f, s))) return rc;
-            if ((rc = launch_box_zero(tmp, tmp2, 3, p->H, p->W, p->D, p->selected_smooth, false, s))) return rc;
-            if ((rc = launch_box_zero(tmp2, tmp, 3, p->H, p->W, p->D, p->selected_smooth, false, s))) return rc;
-            if ((rc = launch_box_zero(tmp, out_field, 3, p->H, p->W, p->D, p->selected_smooth, false, s))) return rc;
-        } else {
-            if ((rc = launch_resize(F(L.U), 3, L.h2, L.w2, L.d2, out_field, p->H, p->W, p->D, (float)p->grid_sp_adam, 1.0f, s))) return rc;
-        }
-        hh = p->H; hw_ = p->W; hd = p->D;
-        mark("upsample", s);
-    } else if (!p->ic) {
-        (void)hipMemcpyAsync(out_field, F(L.soft), sizeof(float) * 3 * L.v, hipMemcpyDeviceToDevice, s);
-    }
-    if (out_dims_host) { out_dims_host[0] = hh; out_dims_host[1] = hw_; out_dims_host[2] = hd; }
-    return check_last("register_pair");
-}
-
 
 // ---- several pairs at once on internal streams ------------------------------------------------------------
 // The kernels of one pair are chained by data dependencies and leave issue slots idle (short grids, tails);
@@ -688,7 +700,6 @@ extern "C" int cvx_convex_stage_f32(const float* feat_fix, const float* feat_mov
     Carver cv(workspace);
     const StageWs L = stage_layout(cv, *p);
     const int h = p->h, w = p->w, d = p->d;
-    const size_t v = (size_t)h * w * d;
     if ((rc = cvx_disp_mesh_f32(p->disp_hw, L.mesh, stream))) return rc;
     // one direction: cost volume + plain argmin of the UNMASKED volume, then the six passes on the masked one (`ssd` is not written)
     auto direction = [&](const float* a, const float* b, const unsigned char* mask, float* soft) -> int {
@@ -706,11 +717,8 @@ extern "C" int cvx_convex_stage_f32(const float* feat_fix, const float* feat_mov
     if ((rc = direction(feat_fix, feat_mov, mask_fix, L.soft))) return rc;
     if ((rc = direction(feat_mov, feat_fix, mask_mov, L.soft2))) return rc;          // (:348-350)
     if ((rc = cvx_affine_base_f32(h, L.bh, stream)) || (rc = cvx_affine_base_f32(w, L.bw, stream)) || (rc = cvx_affine_base_f32(d, L.bd, stream))) return rc;
-    const dim3 gv((unsigned)cdiv64((int64_t)v, 256));
-    hipLaunchKernelGGL(k_ic_prepare, dim3(gv.x, 2), dim3(256), 0, s, L.soft, L.soft2, h, w, d, L.in1, L.in2);          // (disp_soft / scale).flip(1)   (:351)
-    if ((rc = cvx_inverse_consistency_f32(L.in1, L.in2, h, w, d, p->ic_iters, L.bh, L.bw, L.bd, L.ic1, L.ic2, L.ic_ws, L.ic_bytes, stream))) return rc;
     float* up = coarse_field ? coarse_field : L.upin;
-    hipLaunchKernelGGL(k_ic_finish, gv, dim3(256), 0, s, L.ic1, h, w, d, (float)p->grid_sp, up);                       // disp_ice.flip(1) * scale * grid_sp   (:354)
+    if ((rc = ic_tail(L.soft, L.soft2, h, w, d, p->ic_iters, L.bh, L.bw, L.bd, {L.in1, L.in2, L.ic1, L.ic2, L.ic_ws, L.ic_bytes}, (float)p->grid_sp, up, s))) return rc;          // (:351-354)
     if (disp_hr && (rc = launch_resize(up, 3, h, w, d, disp_hr, p->H, p->W, p->D, 1.0f, 1.0f, s))) return rc;
     return check_last("convex_stage");
 }

@@ -226,17 +226,46 @@ def test_contexts_are_per_caller(L):
     ctx.close()
 
 
-def test_every_option_has_its_environment_variable():
-    """The default context reads CVX_<NAME> for every switch (positional initialiser in api.hip): each name must map to its own field."""
+_OPTION_CHILD = ("from convexadam_amd import _lib; L = _lib.lib(); import sys; names = sys.argv[1].split(',');"
+                 "print(','.join(str(L.cvx_get_option(n.encode())) for n in names))")
+
+
+def _options_in_child(names, env):
     import subprocess
     import sys
+    out = subprocess.run([sys.executable, "-c", _OPTION_CHILD, ",".join(names)], env=env, stdout=subprocess.PIPE, text=True, check=True).stdout.strip()
+    return [int(v) for v in out.split(",")]
+
+
+def test_every_option_has_its_environment_variable():
+    """The default context reads CVX_<NAME> for every switch that has a variable (the option list of cvx_common.h): each name must map to
+    its own field, and the two pointer options, which have no variable, read 0."""
     names = ["mind_tiled", "mind_overlap", "mm_tx", "mm_slots", "box_tiled", "no_prune", "corr_unfused", "corr_fused_all", "prune_stream_above",
              "cf_census", "cf_prio", "warp_flat", "box_yt", "box_wg_target", "box_xsplit", "box_cpt", "box_uneven", "box_adam_role", "box_dpp", "box_pk",
-             "box_prio", "label_pow_block", "mind_mean_threads"]
+             "box_prio", "label_pow_block", "mind_mean_threads", "edt_sequential", "warp_octant", "box_fwd_tile", "box_bwd_tile", "box_walk",
+             "corr_dual", "prune_refine", "mind_records", "resize_up2", "mind_blocked", "corr_cert", "cc_debug", "ic_fused", "mind_single",
+             "ms_zlen", "cf_map", "cert_unfused", "fbox_tile", "box_tile_sync", "box_prediv"]
+    assert len(names) == len(set(names)) == 43
     env = dict(os.environ, PYTHONPATH=ROOT)
     for i, n in enumerate(names):
         env["CVX_" + n.upper()] = str(11 + i)
-    code = ("from convexadam_amd import _lib; L = _lib.lib(); import sys; names = sys.argv[1].split(',');"
-            "print(','.join(str(L.cvx_get_option(n.encode())) for n in names + ['census_ptr']))")
-    out = subprocess.run([sys.executable, "-c", code, ",".join(names)], env=env, stdout=subprocess.PIPE, text=True, check=True).stdout.strip()
-    assert out == ",".join(str(11 + i) for i in range(len(names))) + ",0", out
+    env["CVX_CENSUS_PTR"] = env["CVX_TILE_CENSUS_PTR"] = "7"          # no such variables: must not be read
+    got = _options_in_child(names + ["census_ptr", "tile_census_ptr"], env)
+    assert got == [11 + i for i in range(len(names))] + [0, 0], got
+
+
+def test_every_option_has_its_default():
+    """With no CVX_* variable in the environment every switch of the default context holds its documented default (written out here, not
+    read back from the library)."""
+    defaults = [("mind_tiled", 0), ("mind_overlap", 0), ("mm_tx", 0), ("mm_slots", 512), ("box_tiled", 0), ("no_prune", 0), ("corr_unfused", 0),
+                ("corr_fused_all", 0), ("prune_stream_above", -1), ("cf_census", 0), ("cf_prio", 136), ("warp_flat", 0), ("box_yt", 8),
+                ("box_wg_target", 0), ("box_xsplit", -1), ("box_cpt", 4), ("box_uneven", 200), ("box_adam_role", 0), ("box_dpp", 0), ("box_pk", 0),
+                ("box_prio", 0), ("label_pow_block", 32), ("census_ptr", 0), ("mind_mean_threads", 0), ("edt_sequential", 0), ("warp_octant", 4),
+                ("box_fwd_tile", -1), ("box_bwd_tile", -1), ("box_walk", 1), ("corr_dual", 0), ("prune_refine", 1), ("mind_records", 1),
+                ("resize_up2", 1), ("mind_blocked", 1), ("corr_cert", 1), ("cc_debug", 0), ("ic_fused", 0), ("mind_single", 0), ("ms_zlen", 0),
+                ("cf_map", 1), ("cert_unfused", 0), ("fbox_tile", 0), ("box_tile_sync", 0), ("box_prediv", 1), ("tile_census_ptr", 0)]
+    assert len(defaults) == len(set(n for n, _ in defaults)) == 45
+    env = {k: v for k, v in os.environ.items() if not k.startswith("CVX_")}
+    env["PYTHONPATH"] = ROOT
+    got = _options_in_child([n for n, _ in defaults], env)
+    assert got == [v for _, v in defaults], [(n, g, v) for (n, v), g in zip(defaults, got) if g != v]
