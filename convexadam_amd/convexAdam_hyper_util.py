@@ -138,14 +138,16 @@ def jacobian_determinant_3d(dense_flow, convert1=True):
 
 def jacobian_log_std_and_folding(jac_det):
     """convex_run_withconfig.py:148-150: (jac_det.add(3).clamp_(1e-9, 1e9).log().std(), (jac_det < 0).float().mean()) as
-    Python floats; accumulated in float64 on the device."""
+    Python floats; accumulated in float64 on the device.  One element: (nan, .) like torch's unbiased std of a single sample."""
     j = f32c(require_device_tensor(jac_det, "jac_det")).reshape(-1)
     n = int(j.numel())
     acc = torch.empty(3, dtype=torch.float64, device=j.device)
     with torch.cuda.device(j.device):
         check(lib().cvx_jacobian_stats_f64(ptr(j), n, ptr(acc), stream_ptr(j.device)))
     s, s2, neg = [float(v) for v in acc.cpu()]
-    var = max(s2 - s * s / n, 0.0) / max(n - 1, 1)
+    if n == 1:
+        return float("nan"), neg / n
+    var = max(s2 - s * s / n, 0.0) / (n - 1)
     return var ** 0.5, neg / n
 
 

@@ -42,7 +42,8 @@ def jacobian_determinant_3d(flow, convert1=True):
 
 def jacobian_stats(jac_det):
     """convex_run_withconfig.py:148-150: std (unbiased) of log(clamp(jac+3, 1e-9, 1e9)) and the folding fraction.
-    The logarithm and the reduction order of torch are not restated: float64 accumulation, compare at rel 1e-5."""
+    The logarithm and the reduction order of torch are not restated: numpy's two-pass float64 std, which torch's float32 value approaches
+    to float32 accuracy (tests/test_oracle_metrics.py pins both statements)."""
     j = np.asarray(jac_det, f32)
     l = np.log(np.clip((j + f32(3)).astype(f32), f32(1e-9), f32(1e9)).astype(np.float64))
     return float(l.std(ddof=1)), float((j < 0).mean())
@@ -65,8 +66,9 @@ def warp_labels_nearest(seg, disp):
         g = (base[a].reshape(shp) + (disp[a] / sc[a]).astype(f32)).astype(f32)
         pos = (((g + f32(1)) * f32(S)).astype(f32) - f32(1)).astype(f32) / f32(2)       # unnormalize, align_corners=False
         r = np.rint(pos.astype(f32))                                                       # std::nearbyint: half to even
-        ok &= (r >= 0) & (r <= S - 1)
-        idx.append(np.clip(r, 0, S - 1).astype(np.int64))
+        ok_a = (r >= 0) & (r <= S - 1)                                                     # in float, like the kernel: false for NaN
+        ok &= ok_a
+        idx.append(np.where(ok_a, r, 0).astype(np.int64))
     out[ok] = seg[idx[0][ok], idx[1][ok], idx[2][ok]]
     return out
 
@@ -143,10 +145,11 @@ def apply_convex(disp, moving):
     inside = np.ones(mov.shape, bool)
     lo, t = [], []
     for a, S in enumerate((H, W, D)):
-        inside &= (c[a] >= 0) & (c[a] <= S - 1)
-        f = np.floor(c[a])
-        lo.append(np.clip(f, 0, S - 1).astype(np.int64))
-        t.append(c[a] - f)
+        in_a = (c[a] >= 0) & (c[a] <= S - 1)                      # false for NaN and +-inf: those samples are 0
+        inside &= in_a
+        f = np.floor(np.where(in_a, c[a], 0.0))
+        lo.append(f.astype(np.int64))
+        t.append(np.where(in_a, c[a], 0.0) - f)
     out = np.zeros(mov.shape, np.float64)
     m64 = mov.astype(np.float64)
     for i in (0, 1):
