@@ -240,24 +240,50 @@ static void corr_raw_dispatch(const float* Fp, const float* Mp, const CorrGeom& 
     else hipLaunchKernelGGL((k_corr_raw<HW, false>), grid, dim3(256), 0, s, Fp, Mp, g, raw);
 }
 
-// ---- the certified-fast volume: which kernel produces it (option corr_cert: 1 = the role kernel of corrfused.hip in its fast arithmetic
-// without the final scaling -- the faster one as measured --, 2 = the staged kernel of corrcert.hip; 0 in the pipeline = exact volumes) -------
-// ---- C >= 16 with few work items or many channels: the ROUND-1 PAIR OF KERNELS in the certified-fast arithmetic -- k_corr_raw with one FMA per
-// channel (every wavefront on the channel sums, where the role kernel has a third of them) through the raw intermediate, then the two boxes as
-// separable running sums without divisions (corrbox.hip, FAST).  Same class of arithmetic as the role kernel's (C + 13 roundings, non-negative
-// terms only): the certification constants cover it.  Taken when the work is large enough to pay for the certified passes (K v C >= 1e9:
-// BASELINE configs[3], 32 label channels on 40 x 48 x 40 with 729 displacements).
-static bool certfast_unfused_ok(int C, int h, int w, int d, int hw) {
-    if (C < 16 || C > 128 || hw > 8 || options().corr_cert == 2 || options().cert_unfused == 0) return false;
+// ---- which kernel produces a cost volume: ONE plan, read by the size queries, the launchers and the whole-pair pipeline -------------------
+// (the truth table is DESIGN.md's "Path selection of the correlation stage"; measurements behind the rules: tools/time_corr.py,
+// tools/experiments/corr_time_c.py)
+//  exact volume: the fused kernel covers every shape (C up to 255 through the cascade sum, tall planes through y tiles); for C >= 16 its raw
+//    stage -- one third of the wavefronts -- carries most of the work and the round-1 kernels (all wavefronts on the raw SSD, then the box
+//    pipeline) are faster when their raw intermediate is affordable (C = 32 at 26x32x37, hw 6: 0.40 vs 0.63 ms), so they stay the default
+//    there; option corr_fused_all = 1 selects the fused kernel for every C.
+//  certified-fast volume (option corr_cert: 1 = the role kernel of corrfused.hip in its fast arithmetic without the final scaling -- the faster
+//    one as measured --, 2 = the staged kernel of corrcert.hip).  C >= 16 with few work items or many channels: the ROUND-1 PAIR OF KERNELS in
+//    the certified-fast arithmetic -- k_corr_raw with one FMA per channel (every wavefront on the channel sums, where the role kernel has a
+//    third of them) through the raw intermediate, then the two boxes as separable running sums without divisions (corrbox.hip, FAST).  Same
+//    class of arithmetic as the role kernel's (C + 13 roundings, non-negative terms only): the certification constants cover it.  Taken when
+//    the work is large enough to pay for the certified passes (K v C >= 1e9: BASELINE configs[3], 32 label channels on 40 x 48 x 40 with 729
+//    displacements) or always (option cert_unfused = 2).
+//  whole-pair pipeline: the certified path below 16 channels always, from 16 on where a fast kernel beats the exact pair (the role kernel in
+//    the fast arithmetic needs no cascade -- 64 registers, two workgroups per CU -- and wins up to 32 channels where its items fill the chip:
+//    C = 32 at 26x32x37 hw 6 0.36 vs 0.45 ms, C = 16 0.21 vs 0.33; with 162 items (hw 4) or 64 channels it loses -- C = 64 hw 4: 0.56 vs
+//    0.23 ms); corr_cert = 2 keeps the staged kernel selectable for every supported C.
+CorrPlan corr_plan(int C, int h, int w, int d, int hw, CorrUse use) {
+    const Options& o = options();
     const CorrGeom g = corr_geom(C, h, w, d, hw);
-    const size_t K = (size_t)g.n * g.n * g.n;
-    return corr_box2_supported(h, w, d, g.px) && K * h * w * g.px * sizeof(float) <= ((size_t)2 << 30) && ((double)K * h * w * d * C >= 1e9 || options().cert_unfused == 2);
+    const double K = (double)g.n * g.n * g.n;
+    const bool fused_ok = corr_fused_supported(C, h, w, d, hw), staged_ok = corr_cert_supported(C, h, w, d, hw);
+    // the round-1 kernels: k_corr_raw is instantiated for hw <= 8, the box kernel holds rows of limited length, raw [K][h][w][px] stays <= 2 GiB
+    const bool round1_fits = hw <= 8 && corr_box2_supported(h, w, d, g.px) && (size_t)g.n * g.n * g.n * h * w * g.px * sizeof(float) <= ((size_t)2 << 30);
+    const bool role_good = fused_ok && C <= 32 && corr_fused_items(C, h, w, d, hw) >= 384 && !corr_fused_tiled(C, h, w, d, hw);
+    const bool role_ok = fused_ok && C <= 128;        // (the certification bound counts C + 18 roundings, C <= 128)
+    const bool unfused_ok = C >= 16 && C <= 128 && round1_fits && o.corr_cert != 2 && o.cert_unfused != 0 && (K * h * w * d * C >= 1e9 || o.cert_unfused == 2);
+
+    CorrPlan p{};
+    p.exact = (!fused_ok || (!use.variant && o.corr_fused_all == 0 && C >= 16 && round1_fits)) ? CorrKernel::Round1 : CorrKernel::Fused;
+    p.cert = unfused_ok && !role_good                            ? CorrKernel::CertRound1
+             : staged_ok && (o.corr_cert == 2 || !role_ok)       ? CorrKernel::CertStaged
+             : role_ok                                           ? CorrKernel::CertRole
+                                                                 : CorrKernel::None;
+    p.cert_supported = staged_ok || role_ok || unfused_ok;
+    p.fused_ws = fused_ok; p.staged_ws = staged_ok; p.cert_round1_ws = unfused_ok;
+    p.pair_cert = o.corr_cert != 0 && !use.variant && !use.no_prune && p.cert_supported &&
+                  (o.corr_cert == 2 || C < 16 || p.cert == CorrKernel::CertRound1 || role_good);
+    p.pair_dual = use.ic && o.corr_dual != 0 && p.exact == CorrKernel::Fused;
+    p.pair_dual_ws = use.ic && o.corr_dual != 0 && fused_ok;          // (wider than pair_dual: DESIGN.md lists it)
+    return p;
 }
-static bool certfast_use_unfused(int C, int h, int w, int d, int hw) {
-    if (!certfast_unfused_ok(C, h, w, d, hw)) return false;
-    const bool role_good = corr_fused_supported(C, h, w, d, hw) && C <= 32 && corr_fused_items(C, h, w, d, hw) >= 384 && !corr_fused_tiled(C, h, w, d, hw);
-    return !role_good;
-}
+
 // the round-1 kernels' workspace: padded copies, raw SSDs, then (the exact operator) the argmin keys
 struct Round1Ws { float *Fp, *Mp, *raw; unsigned long long* keys; };
 static Round1Ws round1_layout(Carver& cv, int C, int h, int w, int d, int hw, bool keys) {
@@ -269,74 +295,55 @@ static Round1Ws round1_layout(Carver& cv, int C, int h, int w, int d, int hw, bo
     if (keys) r.keys = cv.take<unsigned long long>((size_t)h * w * d);
     return r;
 }
-static size_t certfast_unfused_workspace(int C, int h, int w, int d, int hw) {
-    Carver m; round1_layout(m, C, h, w, d, hw, false); return ws_query(m);
-}
-static int launch_corr_certfast_unfused(const float* fix, const float* mov, int C, int h, int w, int d, int hw, float* ssdu, void* workspace, size_t workspace_bytes,
-                                        hipStream_t s) {
-    if (workspace_bytes < certfast_unfused_workspace(C, h, w, d, hw)) return fail(CVX_ERR_WORKSPACE, "correlate (certified-fast, two kernels): workspace too small");
-    const CorrGeom g = corr_geom(C, h, w, d, hw);
-    const size_t K = (size_t)g.n * g.n * g.n;
-    Carver cv(workspace);
-    const auto [Fp, Mp, raw, no_keys] = round1_layout(cv, C, h, w, d, hw, false);
-    const size_t nprep = (size_t)C * g.hq * g.wq * g.dq;
-    hipLaunchKernelGGL(k_corr_prep, dim3((unsigned)cdiv64((int64_t)nprep, 256)), dim3(256), 0, s, fix, mov, g, Fp, Mp);
-    corr_call_prep_hook(s);
-    switch (hw) {
-        case 0: corr_raw_dispatch<0>(Fp, Mp, g, raw, s, true); break;
-        case 1: corr_raw_dispatch<1>(Fp, Mp, g, raw, s, true); break;
-        case 2: corr_raw_dispatch<2>(Fp, Mp, g, raw, s, true); break;
-        case 3: corr_raw_dispatch<3>(Fp, Mp, g, raw, s, true); break;
-        case 4: corr_raw_dispatch<4>(Fp, Mp, g, raw, s, true); break;
-        case 5: corr_raw_dispatch<5>(Fp, Mp, g, raw, s, true); break;
-        case 6: corr_raw_dispatch<6>(Fp, Mp, g, raw, s, true); break;
-        case 7: corr_raw_dispatch<7>(Fp, Mp, g, raw, s, true); break;
-        default: corr_raw_dispatch<8>(Fp, Mp, g, raw, s, true); break;
+// the round-1 sequence: padded copies, raw SSDs, (exact) ATen's interleaved tail, the two boxes; fast = the certified-fast arithmetic
+static int launch_round1(const float* fix, const float* mov, const CorrGeom& g, const Round1Ws& r, bool fast, float* ssd, hipStream_t s) {
+    const size_t nprep = (size_t)g.C * g.hq * g.wq * g.dq;   // >= nF
+    hipLaunchKernelGGL(k_corr_prep, dim3((unsigned)cdiv64((int64_t)nprep, 256)), dim3(256), 0, s, fix, mov, g, r.Fp, r.Mp);
+    if (fast) corr_call_prep_hook(s);
+    switch (g.hw) {
+        case 0: corr_raw_dispatch<0>(r.Fp, r.Mp, g, r.raw, s, fast); break;
+        case 1: corr_raw_dispatch<1>(r.Fp, r.Mp, g, r.raw, s, fast); break;
+        case 2: corr_raw_dispatch<2>(r.Fp, r.Mp, g, r.raw, s, fast); break;
+        case 3: corr_raw_dispatch<3>(r.Fp, r.Mp, g, r.raw, s, fast); break;
+        case 4: corr_raw_dispatch<4>(r.Fp, r.Mp, g, r.raw, s, fast); break;
+        case 5: corr_raw_dispatch<5>(r.Fp, r.Mp, g, r.raw, s, fast); break;
+        case 6: corr_raw_dispatch<6>(r.Fp, r.Mp, g, r.raw, s, fast); break;
+        case 7: corr_raw_dispatch<7>(r.Fp, r.Mp, g, r.raw, s, fast); break;
+        default: corr_raw_dispatch<8>(r.Fp, r.Mp, g, r.raw, s, fast); break;
     }
-    return launch_corr_box2(raw, (int)K, h, w, d, g.px, ssdu, s, true);
+    // ATen's interleaved tail: last (ncols mod 32) columns of the (h, n^2, w, d) difference tensor
+    const int64_t ncols = (int64_t)g.h * g.n * g.n * g.w * g.d, tail_from = (ncols / 32) * 32;
+    const int ntail = (int)(ncols - tail_from);
+    if (!fast && ntail > 0)
+        hipLaunchKernelGGL(k_corr_tail, dim3(cdiv(ntail * g.n, 64)), dim3(64), 0, s, fix, mov, g, tail_from, ntail, r.raw);
+    return launch_corr_box2(r.raw, g.n * g.n * g.n, g.h, g.w, g.d, g.px, ssd, s, fast);
 }
 
-static bool certfast_use_staged(int C, int h, int w, int d, int hw) {
-    const bool staged_ok = corr_cert_supported(C, h, w, d, hw), fused_ok = corr_fused_supported(C, h, w, d, hw) && C <= 128;
-    if (options().corr_cert == 2) return staged_ok;
-    return staged_ok && !fused_ok;
-}
-bool corr_certfast_supported(int C, int h, int w, int d, int hw) {
-    return corr_cert_supported(C, h, w, d, hw) || (corr_fused_supported(C, h, w, d, hw) && C <= 128) || certfast_unfused_ok(C, h, w, d, hw);
-}
-// does the certified path pay for this geometry in the whole-pair pipeline?  (below 16 channels always; from 16 on where a fast kernel beats the exact pair)
-bool corr_certfast_pays(int C, int h, int w, int d, int hw) {
-    if (C < 16) return true;
-    if (certfast_use_unfused(C, h, w, d, hw)) return true;
-    return C <= 32 && corr_fused_supported(C, h, w, d, hw) && corr_fused_items(C, h, w, d, hw) >= 384 && !corr_fused_tiled(C, h, w, d, hw);
-}
+// the certified-fast volume's workspace is the largest of the kernels' that apply (callers cache the size across option changes of one kernel for another)
 size_t corr_certfast_workspace_bytes(int C, int h, int w, int d, int hw) {
-    const size_t a = corr_cert_supported(C, h, w, d, hw) ? corr_cert_workspace_bytes(C, h, w, d, hw) : 0;
-    const size_t b = corr_fused_supported(C, h, w, d, hw) ? corr_fused_workspace_bytes(C, h, w, d, hw) : 0;
-    const size_t c = certfast_unfused_ok(C, h, w, d, hw) ? certfast_unfused_workspace(C, h, w, d, hw) : 0;
-    return std::max({a, b, c});
+    const CorrPlan p = corr_plan(C, h, w, d, hw);
+    Carver round1;
+    if (p.cert_round1_ws) round1_layout(round1, C, h, w, d, hw, false);
+    return std::max({p.staged_ws ? corr_cert_workspace_bytes(C, h, w, d, hw) : 0, p.fused_ws ? corr_fused_workspace_bytes(C, h, w, d, hw) : 0, ws_query(round1)});
 }
 int launch_corr_certfast(const float* fix, const float* mov, int C, int h, int w, int d, int hw, float* ssdu, void* workspace, size_t workspace_bytes,
                          hipStream_t s) {
-    if (certfast_use_unfused(C, h, w, d, hw)) return launch_corr_certfast_unfused(fix, mov, C, h, w, d, hw, ssdu, workspace, workspace_bytes, s);
-    if (certfast_use_staged(C, h, w, d, hw)) return launch_corr_cert(fix, mov, C, h, w, d, hw, ssdu, workspace, workspace_bytes, s);
-    return launch_corr_fused(fix, mov, C, h, w, d, hw, 0, 2, /*fast=*/2, 0, ssdu, workspace, workspace_bytes, s);
+    switch (corr_plan(C, h, w, d, hw).cert) {
+        case CorrKernel::CertRound1: {
+            Carver cv(workspace);
+            const Round1Ws r = round1_layout(cv, C, h, w, d, hw, false);
+            if (workspace_bytes < ws_query(cv)) return fail(CVX_ERR_WORKSPACE, "correlate (certified-fast, two kernels): workspace too small");
+            return launch_round1(fix, mov, corr_geom(C, h, w, d, hw), r, true, ssdu, s);
+        }
+        case CorrKernel::CertStaged: return launch_corr_cert(fix, mov, C, h, w, d, hw, ssdu, workspace, workspace_bytes, s);
+        default:        // CertRole (None: the callers ask cert_supported first)
+            return launch_corr_fused(fix, mov, C, h, w, d, hw, 0, 2, /*fast=*/2, 0, ssdu, workspace, workspace_bytes, s);
+    }
 }
 
 }  // namespace cvx
 
 using namespace cvx;
-
-// Which path the packaged operator takes.  The fused kernel covers every shape (C up to 255 through the cascade sum, tall planes through
-// y tiles); for C >= 16 its raw stage -- one third of the wavefronts -- carries most of the work and the round-1 kernels (all wavefronts
-// on the raw SSD, then the box pipeline) are faster when their raw intermediate is affordable (tools/time_corr.py: C = 32 at 26x32x37,
-// hw 6: 0.40 vs 0.63 ms), so they stay the default there; option corr_fused_all = 1 selects the fused kernel for every C.
-bool cvx::corr_use_unfused(int C, int h, int w, int d, int hw, bool variant) {
-    if (!corr_fused_supported(C, h, w, d, hw)) return true;
-    if (variant || options().corr_fused_all != 0 || C < 16 || hw > 8) return false;      // (the round-1 raw kernel is instantiated for hw <= 8)
-    const CorrGeom g = corr_geom(C, h, w, d, hw);
-    return corr_box2_supported(h, w, d, g.px) && (size_t)g.n * g.n * g.n * h * w * g.px * sizeof(float) <= ((size_t)2 << 30);
-}
 
 // cvx_correlate_ex_f32's workspace holds one of three layouts: the fused kernel's workspace + the argmin keys; the round-1 kernels'
 // (Round1Ws); or (fast = 2) the certified-fast volume's workspace + the plain certified argmin's.  The query is the largest that applies.
@@ -354,11 +361,11 @@ static PartsWs certified_layout(Carver& cv, int C, int h, int w, int d, int hw) 
     return parts_layout(cv, corr_certfast_workspace_bytes(C, h, w, d, hw), corr_certify_workspace_bytes(C, h, w, d, hw, true));
 }
 extern "C" size_t cvx_correlate_workspace_bytes(int C, int h, int w, int d, int disp_hw) {
+    const CorrPlan p = corr_plan(C, h, w, d, disp_hw);
     Carver fused, round1, cert;
-    const bool fused_ok = corr_fused_supported(C, h, w, d, disp_hw);
-    if (fused_ok) fused_keys_layout(fused, C, h, w, d, disp_hw);
-    if (!fused_ok || corr_use_unfused(C, h, w, d, disp_hw, false)) round1_layout(round1, C, h, w, d, disp_hw, true);
-    if (corr_certfast_supported(C, h, w, d, disp_hw)) certified_layout(cert, C, h, w, d, disp_hw);
+    if (p.fused_ws) fused_keys_layout(fused, C, h, w, d, disp_hw);
+    if (p.exact == CorrKernel::Round1) round1_layout(round1, C, h, w, d, disp_hw, true);
+    if (p.cert_supported) certified_layout(cert, C, h, w, d, disp_hw);
     return std::max({ws_query(fused), ws_query(round1), ws_query(cert)});
 }
 
@@ -382,20 +389,20 @@ extern "C" int cvx_correlate_ex_f32(const float* fix, const float* mov, int C, i
     hipStream_t s = as_stream(stream);
     const CorrGeom g = corr_geom(C, h, w, d, disp_hw);
     const size_t K = (size_t)g.n * g.n * g.n;
+    const bool variant = cost != 0 || n_box != 2 || fast || f16;
+    const CorrPlan plan = corr_plan(C, h, w, d, disp_hw, CorrUse{variant, false, false});
+    Carver cv(workspace);
     if (fast == 2) {
         // certified-fast arithmetic: `ssd` receives the UNSCALED sums (729 x the mean, to within 2^-16 relative); `argmin` -- if asked for --
         // is the reference's argmin (first minimum of the EXACT volume), certified from the fast one and resolved exactly where it cannot be
         if (f16) return fail(CVX_ERR_UNSUPPORTED, "cvx_correlate_ex_f32: the certified-fast volume is float32");
-        if (!corr_certfast_supported(C, h, w, d, disp_hw)) return fail(CVX_ERR_UNSUPPORTED, "cvx_correlate_ex_f32: certified-fast correlation not built for this geometry");
-        Carver cv(workspace);
+        if (!plan.cert_supported) return fail(CVX_ERR_UNSUPPORTED, "cvx_correlate_ex_f32: certified-fast correlation not built for this geometry");
         const PartsWs c = certified_layout(cv, C, h, w, d, disp_hw);
         int rc = launch_corr_certfast(fix, mov, C, h, w, d, disp_hw, ssd, c.a, c.a_bytes, s);
         if (rc || !argmin) return rc;
         return corr_certified_argmin(ssd, fix, mov, C, h, w, d, disp_hw, argmin, c.b, c.b_bytes, s);
     }
-    const bool variant = cost != 0 || n_box != 2 || fast || f16;
-    if (!corr_use_unfused(C, h, w, d, disp_hw, variant)) {
-        Carver cv(workspace);
+    if (plan.exact == CorrKernel::Fused) {
         const PartsWs f = fused_keys_layout(cv, C, h, w, d, disp_hw);
         int rc = launch_corr_fused(fix, mov, C, h, w, d, disp_hw, cost, n_box, fast, f16, ssd, f.a, f.a_bytes, s);
         if (rc) return rc;
@@ -408,30 +415,9 @@ extern "C" int cvx_correlate_ex_f32(const float* fix, const float* mov, int C, i
     if (disp_hw > 8) return fail(CVX_ERR_UNSUPPORTED, "cvx_correlate_f32: disp_hw %d > 8 needs the fused kernel (option corr_unfused is set, or the grid is outside its range: the fused kernel covers rows of d <= ~1270 voxels when the plane has w <= 320 / ceil((d + 6) / 4) rows, else (y tiles) d <= ~250)", disp_hw);
     if (!corr_box2_supported(h, w, d, g.px))
         return fail(CVX_ERR_UNSUPPORTED, "cvx_correlate_f32: coarse rows of %d voxels are too long for the LDS box kernel", d);
-    Carver cv(workspace);
-    const auto [Fp, Mp, raw, keys] = round1_layout(cv, C, h, w, d, disp_hw, true);
-
-    const size_t nprep = (size_t)C * g.hq * g.wq * g.dq;   // >= nF
-    hipLaunchKernelGGL(k_corr_prep, dim3((unsigned)cdiv64((int64_t)nprep, 256)), dim3(256), 0, s, fix, mov, g, Fp, Mp);
-    switch (disp_hw) {
-        case 0: corr_raw_dispatch<0>(Fp, Mp, g, raw, s); break;
-        case 1: corr_raw_dispatch<1>(Fp, Mp, g, raw, s); break;
-        case 2: corr_raw_dispatch<2>(Fp, Mp, g, raw, s); break;
-        case 3: corr_raw_dispatch<3>(Fp, Mp, g, raw, s); break;
-        case 4: corr_raw_dispatch<4>(Fp, Mp, g, raw, s); break;
-        case 5: corr_raw_dispatch<5>(Fp, Mp, g, raw, s); break;
-        case 6: corr_raw_dispatch<6>(Fp, Mp, g, raw, s); break;
-        case 7: corr_raw_dispatch<7>(Fp, Mp, g, raw, s); break;
-        default: corr_raw_dispatch<8>(Fp, Mp, g, raw, s); break;
-    }
-    // ATen's interleaved tail: last (ncols mod 32) columns of the (h, n^2, w, d) difference tensor
-    const int64_t ncols = (int64_t)h * g.n * g.n * w * d, tail_from = (ncols / 32) * 32;
-    const int ntail = (int)(ncols - tail_from);
-    if (ntail > 0)
-        hipLaunchKernelGGL(k_corr_tail, dim3(cdiv(ntail * g.n, 64)), dim3(64), 0, s, fix, mov, g, tail_from, ntail, raw);
-
-    int rc = launch_corr_box2(raw, (int)K, h, w, d, g.px, ssd, s);
+    const Round1Ws r = round1_layout(cv, C, h, w, d, disp_hw, true);
+    int rc = launch_round1(fix, mov, g, r, false, ssd, s);
     if (rc) return rc;
-    if (argmin) return launch_argmin(ssd, false, nullptr, nullptr, 0.0f, false, (int)K, (size_t)h * w * d, keys, argmin, s);
+    if (argmin) return launch_argmin(ssd, false, nullptr, nullptr, 0.0f, false, (int)K, (size_t)h * w * d, r.keys, argmin, s);
     return CVX_OK;
 }

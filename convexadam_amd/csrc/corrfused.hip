@@ -512,12 +512,10 @@ bool corr_fused_supported(int C, int h, int w, int d, int hw) {
     return (size_t)C * g.hq * g.wq * g.dq * 4 + 64 < ((size_t)1 << 31) && (size_t)h * w * d * 4 < ((size_t)1 << 31);
 }
 
-// work items of one launch (0: geometry not supported) -- the callers' measure of whether the kernel fills the 2 x 256 workgroup slots
-int corr_fused_items(int C, int h, int w, int d, int hw) {
-    if (!corr_fused_supported(C, h, w, d, hw)) return 0;
-    const CFGeom g = cf_geom(C, h, w, d, hw);
-    return g.n * g.n * g.ng * (g.nyt > 0 ? g.nyt : 1);
-}
+// work items of one launch: (dH, dW) pairs x groups of D-shifts x y tiles (a geometry too tall for any tile -- nyt = 0, unsupported -- counts one)
+static int cf_items(const CFGeom& g) { return g.n * g.n * g.ng * (g.nyt > 0 ? g.nyt : 1); }
+// (0: geometry not supported) -- the plan's measure of whether the kernel fills the 2 x 256 workgroup slots
+int corr_fused_items(int C, int h, int w, int d, int hw) { return corr_fused_supported(C, h, w, d, hw) ? cf_items(cf_geom(C, h, w, d, hw)) : 0; }
 
 bool corr_fused_tiled(int C, int h, int w, int d, int hw) { return cf_geom(C, h, w, d, hw).tiled != 0; }
 
@@ -528,7 +526,7 @@ static CFWs cf_layout(Carver& cv, const CFGeom& g, int C, int h, int w) {
     f.Fp = cv.take<float>((size_t)C * h * w * g.RS);
     f.Mp = cv.take<float>((size_t)C * g.hq * g.wq * g.dq + 8);
     f.tail = cv.take<float>((size_t)32 * g.n);
-    f.census = cv.take<unsigned long long>((size_t)4 * (g.n * g.n * g.ng * (g.nyt > 0 ? g.nyt : 1) + 8));
+    f.census = cv.take<unsigned long long>((size_t)4 * (cf_items(g) + 8));
     return f;
 }
 size_t corr_fused_workspace_bytes(int C, int h, int w, int d, int hw) { Carver m; cf_layout(m, cf_geom(C, h, w, d, hw), C, h, w); return ws_query(m); }
@@ -544,7 +542,7 @@ static void cf_launch_c(const CFGeom& gl, const float* Fp, const float* Mp, cons
     const size_t lds = sizeof(float) * (16 + (ONEBOX ? 1 : 2) * (size_t)(CF_GMAX + 2) * gl.PF);
     static size_t granted = 0;
     ensure_dynamic_lds(&k_corr_fused<CF_GMAX, MODE, CASC, TILED>, lds, granted);
-    const int items = gl.n * gl.n * gl.ng * gl.nyt;
+    const int items = cf_items(gl);
     CFSecond two = {nullptr, nullptr, nullptr, nullptr, 0};
     if (second) { two = *second; two.items1 = items; }
     hipLaunchKernelGGL((k_corr_fused<CF_GMAX, MODE, CASC, TILED>), dim3(second ? 2 * items : (gl.colocate ? 512 : items)), dim3((ONEBOX ? 2 : 3) * 64 * gl.wpr), lds, s, Fp, Mp, tail, gl, ssd, two);

@@ -459,10 +459,10 @@ int launch_corr_box2(const float* raw, int K, int h, int w, int d, int px, float
 // corrfused.hip: raw SSD + both boxes in one kernel (C < 16, planes of at most 320 quads); else the unfused path above
 bool corr_fused_supported(int C, int h, int w, int d, int hw);
 void corr_fused_set_prep_hook(void (*hook)(hipStream_t));         // profiling: called between the feature copies and the fused kernel (per thread; nullptr = off)
+// work items of one launch of the fused kernel (0: unsupported geometry) and whether its planes are cut into y tiles (halo rows recomputed)
 int corr_fused_items(int C, int h, int w, int d, int hw);
-bool corr_fused_tiled(int C, int h, int w, int d, int hw);          // planes cut into y tiles (halo rows recomputed)
+bool corr_fused_tiled(int C, int h, int w, int d, int hw);
 void corr_call_prep_hook(hipStream_t s);                            // the hook of corr_fused_set_prep_hook, for the other correlation paths
-bool corr_certfast_pays(int C, int h, int w, int d, int hw);        // (correlate.hip) the whole-pair pipeline's rule for taking the certified path            // work items of one launch of the fused kernel (0: unsupported geometry)
 size_t corr_fused_workspace_bytes(int C, int h, int w, int d, int hw);
 int launch_corr_fused(const float* fix, const float* mov, int C, int h, int w, int d, int hw, int cost, int n_box, int fast, int f16,
                       void* ssd, void* workspace, size_t workspace_bytes, hipStream_t s);
@@ -474,8 +474,19 @@ bool corr_cert_supported(int C, int h, int w, int d, int hw);
 size_t corr_cert_workspace_bytes(int C, int h, int w, int d, int hw);
 int launch_corr_cert(const float* fix, const float* mov, int C, int h, int w, int d, int hw, float* ssdu, void* workspace, size_t workspace_bytes,
                      hipStream_t s);
-// correlate.hip: the certified-fast volume from whichever kernel option corr_cert selects
-bool corr_certfast_supported(int C, int h, int w, int d, int hw);
+// correlate.hip: WHICH KERNEL produces a cost volume -- decided once, for the size queries, the launchers and the whole-pair pipeline
+// (truth table: DESIGN.md, "Path selection of the correlation stage")
+enum class CorrKernel { None, Fused, Round1, CertRole, CertStaged, CertRound1 };
+struct CorrUse { bool variant, ic, no_prune; };     // the caller: a cost / n_box / fast / fp16 variant of the operator, an inverse-consistent pair, option no_prune
+struct CorrPlan {
+    CorrKernel exact;            // cvx_correlate_ex_f32 with fast 0 / 1 (Round1 refuses variants, hw > 8 and rows too long for the box kernel)
+    CorrKernel cert;             // the certified-fast volume (fast 2); None: no kernel built for this geometry
+    bool cert_supported;         // fast 2 is accepted
+    bool fused_ws, staged_ws, cert_round1_ws;   // the workspaces a size query counts (the largest layout that applies, not only the chosen kernel's)
+    bool pair_cert;              // the whole-pair pipeline takes the certified path
+    bool pair_dual, pair_dual_ws;               // ... evaluates both directions in one launch of the fused kernel / reserves the second workspace for it
+};
+CorrPlan corr_plan(int C, int h, int w, int d, int hw, CorrUse use = CorrUse{false, false, false});
 size_t corr_certfast_workspace_bytes(int C, int h, int w, int d, int hw);
 int launch_corr_certfast(const float* fix, const float* mov, int C, int h, int w, int d, int hw, float* ssdu, void* workspace, size_t workspace_bytes,
                          hipStream_t s);
@@ -487,8 +498,6 @@ int corr_certified_argmin(const float* ssdu, const float* fix, const float* mov,
 int coupled_convex_cert_impl(const float* ssduA, const float* fixA, const float* movA, float* outA, void* wsA, const float* ssduB, const float* fixB,
                              const float* movB, float* outB, void* wsB, const float* mesh, int C, int h, int w, int d, int hw, size_t workspace_bytes,
                              hipStream_t s, int stage = 0);      // stage 0 = everything, 1..5 = arm / stream A / stream B / certify the plain argmin / coupled passes
-// correlate.hip: would cvx_correlate_ex_f32 take the unfused round-1 kernels for this problem?
-bool corr_use_unfused(int C, int h, int w, int d, int hw, bool variant);
 // boxmarch.hip: three chained 3^3 boxes (forward / adjoint / adjoint + Adam) for rows of at most 126 voxels
 bool box3_march_supported(int d);
 int launch_box3_march(const float* in, float* out, int h, int w, int d, bool backward, float* P, float* m, float* v,

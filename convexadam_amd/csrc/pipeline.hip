@@ -124,7 +124,7 @@ static PairLayout pair_layout(const cvx_pair_params& p, int n_snap = 0, int max_
     L.ms = cv.take_bytes(f * L.C * L.v);
     L.corr_ws = cv.take_bytes(cvx_correlate_workspace_bytes(L.C, L.h, L.w, L.d, p.disp_hw));
     // the reverse direction's padded copies (both directions in one launch): only where that path can run (option corr_dual, off by default)
-    L.corr_ws2 = (p.ic && options().corr_dual != 0 && corr_fused_supported(L.C, L.h, L.w, L.d, p.disp_hw)) ? cv.take_bytes(corr_fused_workspace_bytes(L.C, L.h, L.w, L.d, p.disp_hw)) : 0;
+    L.corr_ws2 = corr_plan(L.C, L.h, L.w, L.d, p.disp_hw, CorrUse{false, p.ic != 0, false}).pair_dual_ws ? cv.take_bytes(corr_fused_workspace_bytes(L.C, L.h, L.w, L.d, p.disp_hw)) : 0;
     // fp16 storage: the cost volumes hold __half (half the bytes written by the correlation kernel and read by every argmin pass)
     const size_t ssd_elem = p.fp16_storage ? 2 : f;
     L.ssd = cv.take_bytes(ssd_elem * (size_t)L.K * L.v);
@@ -403,13 +403,9 @@ struct PairRun {
         // Certified-fast path (option corr_cert, default): the cost volumes in the fast arithmetic (unscaled, 2^-16 relative to ATen's), every
         // argmin decision certified against the exact arithmetic or evaluated exactly (certify.hip) -- the SAME winners, hence the same field bits,
         // as the exact kernels below; packaged operator only (SSD, two boxes, float32, pruned passes).
-        // (C >= 16: the role kernel carries the channel sums in a third of its wavefronts.  In the fast arithmetic it needs no cascade -- 64 registers, two
-        // workgroups per CU -- and beats the exact kernels up to 32 channels where its items fill the chip: C = 32 at 26x32x37 hw 6 0.36 vs 0.45 ms,
-        // C = 16 0.21 vs 0.33; with 162 items (hw 4) or 64 channels it loses -- C = 64 hw 4: 0.56 vs 0.23 ms --, tools/experiments/corr_time_c.py;
-        // corr_cert = 2 keeps the staged kernel selectable for every supported C)
-        const bool cert = options().corr_cert != 0 && !variant && !no_prune() && corr_certfast_supported(L.C, L.h, L.w, L.d, p->disp_hw) &&
-                          (options().corr_cert == 2 || corr_certfast_pays(L.C, L.h, L.w, L.d, p->disp_hw));
-        if (cert) {
+        // (which geometries take it, and with which kernel: corr_plan, correlate.hip)
+        const CorrPlan plan = corr_plan(L.C, L.h, L.w, L.d, p->disp_hw, CorrUse{variant, p->ic != 0, no_prune()});
+        if (plan.pair_cert) {
             const size_t fws = corr_certfast_workspace_bytes(L.C, L.h, L.w, L.d, p->disp_hw), qws = corr_certify_workspace_bytes(L.C, L.h, L.w, L.d, p->disp_hw);
             auto cert_stage = [&](int stage) {
                 return coupled_convex_cert_impl(F(L.ssd), F(L.fs), F(L.ms), F(L.soft), ws + L.cert_ws, p->ic ? F(L.ssd2) : nullptr, F(L.ms), F(L.fs),
@@ -431,8 +427,7 @@ struct PairRun {
         }
         // Both directions' cost volumes in ONE launch of the fused kernel when the pair is inverse consistent (option corr_dual): the stage
         // interval "correlate" then covers both directions and "correlate_rev" is not recorded.
-        const bool dual = p->ic && options().corr_dual != 0 && !corr_use_unfused(L.C, L.h, L.w, L.d, p->disp_hw, variant) && p->disp_hw <= CVX_MAX_DISP_HW;
-        if (dual) {
+        if (plan.pair_dual) {
             const size_t fws = corr_fused_workspace_bytes(L.C, L.h, L.w, L.d, p->disp_hw);
             if ((rc = launch_corr_fused_dual(F(L.fs), F(L.ms), L.C, L.h, L.w, L.d, p->disp_hw, copt.cost, copt.n_box, copt.fast, copt.f16, F(L.ssd), F(L.ssd2),
                                              ws + L.corr_ws, fws, ws + L.corr_ws2, s))) return rc;
