@@ -88,6 +88,7 @@ SIGNATURES = {
     "cvx_label_histogram_i64": (_i, [_vp, _i64, _i, _vp, _vp]),
     "cvx_label_weights_host": (_i, [_vp, _vp, _i, _vp, _vp]),
     "cvx_label_features_f32": (_i, [_vp, _i64, _i, _vp, _vp, _f, _vp, _vp]),
+    "cvx_label_features_pooled_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _f, _i, _vp, _i, _vp, _vp]),
     "cvx_correlate_workspace_bytes": (_sz, [_i] * 5),
     "cvx_correlate_ex_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "cvx_correlate_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
@@ -118,6 +119,8 @@ SIGNATURES = {
     "cvx_box3_fast_f32": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "cvx_register_pair_workspace_bytes": (_sz, [C.POINTER(PairParams)]),
     "cvx_register_pair_f32": (_i, [_vp, _vp, _vp, _vp, C.POINTER(PairParams), _vp, _vp, _vp, _sz, _vp]),
+    "cvx_register_label_pair_workspace_bytes": (_sz, [C.POINTER(PairParams)]),
+    "cvx_register_label_pair_f32": (_i, [_vp, _vp, _vp, _vp, _f, C.POINTER(PairParams), _vp, _vp, _vp, _sz, _vp]),
     "cvx_register_pair_snapshots_workspace_bytes": (_sz, [_vp, _i, _vp, _i]),
     "cvx_register_pair_snapshots_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _sz, _vp]),
     "cvx_register_pairs_f32": (_i, [_i, _vp, _vp, _vp, _vp, C.POINTER(PairParams), _vp, _vp, _vp, _sz, _i, _vp]),

@@ -169,6 +169,45 @@ def _field_shape(H, W, D, grid_sp, ic, lambda_weight):
     return (3, H, W, D) if ic or lambda_weight > 0 else (3, H // grid_sp, W // grid_sp, D // grid_sp)
 
 
+def _register_device(query, launch, again, n_feat, H, W, D, dev, mind_r, mind_d, lambda_weight, grid_sp, disp_hw, selected_niter, selected_smooth,
+                     grid_sp_adam, ic, cost_scale, out, profile, cost, n_box, n_spline_pools, corr_mode, storage, adam_mode):
+    """What the single-pair device entries share (register_pair_device here, convex_adam_nnUNet.register_labels_device): the reference's
+    behaviour for option values it does not handle, struct cvx_pair_params, workspace and output, the call.  `query`: the entry's
+    workspace query; `launch(p, out, dims, ws, nws)`: its C call, returns the status; `again(selected_smooth, out)`: the same public
+    call with these two arguments replaced.  (The caller has checked that `dev` is a HIP device.)"""
+    if lambda_weight > 0 and selected_niter < 1:
+        # the reference reads `disp_sample` after a loop that never ran (:181)
+        raise UnboundLocalError("local variable 'disp_sample' referenced before assignment "
+                                "(selected_niter=0 with lambda_weight>0, convex_adam_MIND.py:181)")
+    if selected_smooth > 0 and selected_smooth % 2 == 0:
+        # The reference announces "+1" for an even kernel and then overwrites its own fix (:185-189): three avg_pool3d(k, stride 1,
+        # padding k//2) that each make every axis one voxel longer -- it returns (H+3, W+3, D+3, 3).  Restated as it behaves: the pair
+        # without smoothing, then the three growing pools (cvx_box_grow_f32).  With lambda_weight <= 0 the block is never reached (:155).
+        from .convex_adam_utils import box_smooth
+        if out is not None and lambda_weight > 0:
+            raise ValueError("register_pair_device: an even selected_smooth returns a (3,H+3,W+3,D+3) field; `out` is not supported")
+        disp = again(0, out)
+        return box_smooth(disp[None], int(selected_smooth), 3)[0] if lambda_weight > 0 else disp
+    adam_mode = _resolve_adam_mode(adam_mode, n_spline_pools, storage)
+    if cost not in ("ssd", "sad") or corr_mode not in ("exact", "fast") or storage not in ("fp32", "fp16") or adam_mode not in ("exact", "fast", "fast_all"):
+        raise ValueError("cost must be 'ssd' or 'sad', corr_mode 'exact' or 'fast', adam_mode 'exact', 'fast' or 'fast_all', storage 'fp32' or 'fp16'")
+    p = _pair_params(adam_mode, cost, corr_mode, storage, H=H, W=W, D=D, mind_r=mind_r, mind_d=mind_d, lambda_weight=lambda_weight, grid_sp=grid_sp,
+                     disp_hw=disp_hw, selected_niter=selected_niter, selected_smooth=selected_smooth, grid_sp_adam=grid_sp_adam, ic=bool(ic),
+                     n_feat=n_feat, cost_scale=cost_scale, n_box=n_box, n_spline_pools=n_spline_pools)
+    nws = _workspace_bytes(query, C.byref(p))
+    oshape = _field_shape(H, W, D, grid_sp, ic, lambda_weight)
+    if out is None:
+        out = torch.empty(oshape, dtype=torch.float32, device=dev)
+    ws = workspace(nws, dev)
+    dims = (C.c_int * 3)()
+    with torch.cuda.device(dev):
+        if profile is not None:
+            lib().cvx_set_profiling(int(profile))
+        check(launch(C.byref(p), ptr(out), C.cast(dims, C.c_void_p), ptr(ws), nws, stream_ptr(dev)))
+    assert tuple(dims) == tuple(oshape[1:]), (tuple(dims), oshape)
+    return out
+
+
 def register_pair_device(img_fixed=None, img_moving=None, feat_fixed=None, feat_moving=None, mind_r=1, mind_d=2,
                          lambda_weight=1.25, grid_sp=6, disp_hw=4, selected_niter=80, selected_smooth=0, grid_sp_adam=2,
                          ic=True, cost_scale=12.0, out=None, profile=None, cost="ssd", n_box=2, n_spline_pools=3, corr_mode="exact",
@@ -183,41 +222,14 @@ def register_pair_device(img_fixed=None, img_moving=None, feat_fixed=None, feat_
     a, b, ff, fm, n_feat, H, W, D, dev = _unpack_pair(img_fixed, img_moving, feat_fixed, feat_moving,
                                                       "register_pair_device expects two (H,W,D) volumes of equal shape")
     _require_hip(dev)
-    if lambda_weight > 0 and selected_niter < 1:
-        # the reference reads `disp_sample` after a loop that never ran (:181)
-        raise UnboundLocalError("local variable 'disp_sample' referenced before assignment "
-                                "(selected_niter=0 with lambda_weight>0, convex_adam_MIND.py:181)")
-    if selected_smooth > 0 and selected_smooth % 2 == 0:
-        # The reference announces "+1" for an even kernel and then overwrites its own fix (:185-189): three avg_pool3d(k, stride 1,
-        # padding k//2) that each make every axis one voxel longer -- it returns (H+3, W+3, D+3, 3).  Restated as it behaves: the pair
-        # without smoothing, then the three growing pools (cvx_box_grow_f32).  With lambda_weight <= 0 the block is never reached (:155).
-        from .convex_adam_utils import box_smooth
-        if out is not None and lambda_weight > 0:
-            raise ValueError("register_pair_device: an even selected_smooth returns a (3,H+3,W+3,D+3) field; `out` is not supported")
-        disp = register_pair_device(img_fixed, img_moving, feat_fixed, feat_moving, mind_r, mind_d, lambda_weight, grid_sp, disp_hw,
-                                    selected_niter, 0, grid_sp_adam, ic, cost_scale, out, profile, cost, n_box, n_spline_pools, corr_mode,
-                                    storage, adam_mode)
-        return box_smooth(disp[None], int(selected_smooth), 3)[0] if lambda_weight > 0 else disp
-    adam_mode = _resolve_adam_mode(adam_mode, n_spline_pools, storage)
-    if cost not in ("ssd", "sad") or corr_mode not in ("exact", "fast") or storage not in ("fp32", "fp16") or adam_mode not in ("exact", "fast", "fast_all"):
-        raise ValueError("cost must be 'ssd' or 'sad', corr_mode 'exact' or 'fast', adam_mode 'exact', 'fast' or 'fast_all', storage 'fp32' or 'fp16'")
-    p = _pair_params(adam_mode, cost, corr_mode, storage, H=H, W=W, D=D, mind_r=mind_r, mind_d=mind_d, lambda_weight=lambda_weight, grid_sp=grid_sp,
-                     disp_hw=disp_hw, selected_niter=selected_niter, selected_smooth=selected_smooth, grid_sp_adam=grid_sp_adam, ic=bool(ic),
-                     n_feat=n_feat, cost_scale=cost_scale, n_box=n_box, n_spline_pools=n_spline_pools)
     L = lib()
-    nws = _workspace_bytes(L.cvx_register_pair_workspace_bytes, C.byref(p))
-    oshape = _field_shape(H, W, D, grid_sp, ic, lambda_weight)
-    if out is None:
-        out = torch.empty(oshape, dtype=torch.float32, device=dev)
-    ws = workspace(nws, dev)
-    dims = (C.c_int * 3)()
-    with torch.cuda.device(dev):
-        if profile is not None:
-            L.cvx_set_profiling(int(profile))
-        check(L.cvx_register_pair_f32(ptr(a), ptr(b), ptr(ff), ptr(fm), C.byref(p), ptr(out), C.cast(dims, C.c_void_p), ptr(ws), nws,
-                                      stream_ptr(dev)))
-    assert tuple(dims) == tuple(oshape[1:]), (tuple(dims), oshape)
-    return out
+    return _register_device(
+        L.cvx_register_pair_workspace_bytes, lambda *tail: L.cvx_register_pair_f32(ptr(a), ptr(b), ptr(ff), ptr(fm), *tail),
+        lambda smooth, out_: register_pair_device(img_fixed, img_moving, feat_fixed, feat_moving, mind_r, mind_d, lambda_weight, grid_sp, disp_hw,
+                                                  selected_niter, smooth, grid_sp_adam, ic, cost_scale, out_, profile, cost, n_box, n_spline_pools,
+                                                  corr_mode, storage, adam_mode),
+        n_feat, H, W, D, dev, mind_r, mind_d, lambda_weight, grid_sp, disp_hw, selected_niter, selected_smooth, grid_sp_adam, ic, cost_scale, out,
+        profile, cost, n_box, n_spline_pools, corr_mode, storage, adam_mode)
 
 
 def register_pair_snapshots_device(img_fixed=None, img_moving=None, feat_fixed=None, feat_moving=None, snapshot_iters=(40, 60, 80),

@@ -453,6 +453,9 @@ int launch_mind_pooled(const float* img, int H, int W, int D, int radius, int di
                        float* raw, void* workspace, size_t workspace_bytes, hipStream_t s, int records = 0);   // records 1 / 2: out2 = float32 / half feature records
 bool mind_pooled_records_supported(int H, int W, int D, int g1, int g2);
 size_t mind_pooled_raw_floats(int H, int W, int D, int g1, int g2);      // floats of launch_mind_pooled's `raw` scratch (>= 12 H W D: blocked tiles overhang)
+// labelpool.hip: weighted one-hot label features delivered only through their stride poolings (g2 == 0 / out2 null: one pooling); no workspace
+int launch_label_pooled(const float* lab, int H, int W, int D, int C, const int* present, const float* weights, float mult, int g1, float* out1,
+                        int g2, float* out2, hipStream_t s);
 // corrbox.hip: the two box filters of the SSD volume (z-marching pipeline); raw [K][h][w][px] -> ssd [K][h][w][d]
 bool corr_box2_supported(int h, int w, int d, int px);
 int launch_corr_box2(const float* raw, int K, int h, int w, int d, int px, float* ssd, hipStream_t s, bool fast = false);   // fast: separable running sums, no divisions (certified-fast arithmetic)

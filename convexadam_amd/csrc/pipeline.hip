@@ -122,6 +122,9 @@ static PairLayout pair_layout(const cvx_pair_params& p, int n_snap = 0, int max_
     }
     L.fs = cv.take_bytes(f * L.C * L.v);
     L.ms = cv.take_bytes(f * L.C * L.v);
+    // ---- scratch of the convex stage alone: nothing in it is read once the coupled-convex solves are enqueued (PairRun::convex), so
+    // the Adam loop's workspace, first touched after them on the same stream, lies over it (adam_ws below)
+    const size_t convex_scratch = align_up(cv.used, 256);
     L.corr_ws = cv.take_bytes(cvx_correlate_workspace_bytes(L.C, L.h, L.w, L.d, p.disp_hw));
     // the reverse direction's padded copies (both directions in one launch): only where that path can run (option corr_dual, off by default)
     L.corr_ws2 = corr_plan(L.C, L.h, L.w, L.d, p.disp_hw, CorrUse{false, p.ic != 0, false}).pair_dual_ws ? cv.take_bytes(corr_fused_workspace_bytes(L.C, L.h, L.w, L.d, p.disp_hw)) : 0;
@@ -133,14 +136,22 @@ static PairLayout pair_layout(const cvx_pair_params& p, int n_snap = 0, int max_
     L.conv_ws = cv.take_bytes(cvx_coupled_convex_workspace_bytes(L.h, L.w, L.d, p.disp_hw));
     // certified decisions on the fast cost volume (certify.hip): one small workspace per direction
     L.cert_ws = cv.take_bytes(corr_certify_workspace_bytes(L.C, L.h, L.w, L.d, p.disp_hw));
-    if (p.ic) L.cert_ws2 = cv.take_bytes(corr_certify_workspace_bytes(L.C, L.h, L.w, L.d, p.disp_hw));
-    L.soft = cv.take_bytes(f * 3 * L.v);
-    L.bh = cv.take_bytes(f * L.h); L.bw = cv.take_bytes(f * L.w); L.bd = cv.take_bytes(f * L.d);
     if (p.ic) {
+        L.cert_ws2 = cv.take_bytes(corr_certify_workspace_bytes(L.C, L.h, L.w, L.d, p.disp_hw));
         // the reverse direction keeps its own cost volume: both coupled-convex solves share their launches
         L.ssd2 = cv.take_bytes(ssd_elem * (size_t)L.K * L.v);
         L.argmin2 = cv.take_bytes(sizeof(int64_t) * L.v);
         L.conv_ws2 = cv.take_bytes(cvx_coupled_convex_workspace_bytes(L.h, L.w, L.d, p.disp_hw));
+    }
+    if (p.lambda_weight > 0) {
+        Carver over; over.used = convex_scratch;
+        L.adam_ws = over.take_bytes(cvx_adam_workspace_bytes(L.C, L.h2, L.w2, L.d2));
+        if (over.used > cv.used) cv.used = over.used;
+    }
+    // ---- what outlives the convex stage
+    L.soft = cv.take_bytes(f * 3 * L.v);
+    L.bh = cv.take_bytes(f * L.h); L.bw = cv.take_bytes(f * L.w); L.bd = cv.take_bytes(f * L.d);
+    if (p.ic) {
         L.soft2 = cv.take_bytes(f * 3 * L.v);
         L.in1 = cv.take_bytes(f * 3 * L.v); L.in2 = cv.take_bytes(f * 3 * L.v);
         L.ic1 = cv.take_bytes(f * 3 * L.v); L.ic2 = cv.take_bytes(f * 3 * L.v);
@@ -154,7 +165,6 @@ static PairLayout pair_layout(const cvx_pair_params& p, int n_snap = 0, int max_
         L.F2 = cv.take_bytes(f2_bytes);
         L.M2 = cv.take_bytes(f2_bytes);
         L.P = cv.take_bytes(f * 3 * L.V2); L.m = cv.take_bytes(f * 3 * L.V2); L.v_ = cv.take_bytes(f * 3 * L.V2); L.U = cv.take_bytes(f * 3 * L.V2);
-        L.adam_ws = cv.take_bytes(cvx_adam_workspace_bytes(L.C, L.h2, L.w2, L.d2));
         L.bh2 = cv.take_bytes(f * L.h2); L.bw2 = cv.take_bytes(f * L.w2); L.bd2 = cv.take_bytes(f * L.d2);
         if (p.selected_smooth > 0 || max_smooth > 0) { L.smooth_ws = cv.take_bytes(f * 3 * L.V); L.smooth_ws2 = cv.take_bytes(f * 3 * L.V); }
         if (n_snap > 0) L.snaps = cv.take_bytes(f * 3 * L.V2 * (size_t)n_snap);
@@ -300,6 +310,9 @@ static int ic_tail(const float* soft, const float* soft2, int h, int w, int d, i
     return CVX_OK;
 }
 
+// the label entry's inputs: two label maps [H][W][D], the channels' labels and weights (device [C]), the features' multiplier
+struct LabelPair { const float *fixed, *moving; const int* present; const float* weights; float mult; };
+
 // One call of register_pair_core: what every step reads and what a step leaves for a later one; the steps are its member functions, in the order they run.
 namespace {
 struct PairRun {
@@ -308,9 +321,11 @@ struct PairRun {
     char* ws;
     hipStream_t s;
     const float *featF, *featM;             // full-resolution features: the caller's, or the MIND descriptors where they are written
+    const LabelPair* labels;                // label entry: the pooled one-hot features come straight from the two label maps
     bool pooled_mind = false, mind_records = false;
     CoupledWs cw1{}, cw2{};                 // coupled-convex workspaces of the two directions (the plain argmin leaves its keys in their first key buffer)
 
+    bool pooled() const { return pooled_mind || labels != nullptr; }      // fs / ms (and F2 / M2) are written by `features`
     bool no_prune() const { return options().no_prune != 0; }        // streaming coupled passes need int64 winners
     bool f16() const { return p->fp16_storage != 0; }
     float* F(size_t off) const { return reinterpret_cast<float*>(ws + off); }
@@ -351,8 +366,16 @@ struct PairRun {
             }
             featF = F(L.featF); featM = F(L.featM);
         }
-        mark("mind", s);
-        if (!pooled_mind) {
+        if (labels) {
+            // label path: the weighted one-hot volumes are consumed only through the same two poolings and are never written either
+            const int g2 = adam ? p->grid_sp_adam : 0;
+            if ((rc = launch_label_pooled(labels->fixed, p->H, p->W, p->D, L.C, labels->present, labels->weights, labels->mult, p->grid_sp, F(L.fs), g2,
+                                          adam ? F(L.F2) : nullptr, s))) return rc;
+            if ((rc = launch_label_pooled(labels->moving, p->H, p->W, p->D, L.C, labels->present, labels->weights, labels->mult, p->grid_sp, F(L.ms), g2,
+                                          adam ? F(L.M2) : nullptr, s))) return rc;
+        }
+        mark(labels ? "label_features" : "mind", s);
+        if (!pooled()) {
             if ((rc = cvx_avgpool_f32(featF, L.C, p->H, p->W, p->D, p->grid_sp, F(L.fs), s))) return rc;
             if ((rc = cvx_avgpool_f32(featM, L.C, p->H, p->W, p->D, p->grid_sp, F(L.ms), s))) return rc;
         }
@@ -457,7 +480,7 @@ struct PairRun {
     // Adam instance optimisation and the full-resolution output                   (:147-191)
     int adam_and_output(const int* snap_iters_host, int n_snap, const int* smooth_host, int n_smooth, float* out_field) {
         int rc;
-        if (!pooled_mind) {
+        if (!pooled()) {
             if ((rc = cvx_avgpool_f32(featF, L.C, p->H, p->W, p->D, p->grid_sp_adam, F(L.F2), s))) return rc;
             if ((rc = cvx_avgpool_f32(featM, L.C, p->H, p->W, p->D, p->grid_sp_adam, F(L.M2), s))) return rc;
         }
@@ -491,12 +514,14 @@ struct PairRun {
 // listed Adam iteration the up-sampled disp_sample of that iteration, once per listed final smoothing (0 = none, k = three k^3 boxes)
 static int register_pair_core(const float* img_fixed, const float* img_moving, const float* feat_fixed, const float* feat_moving,
                               const cvx_pair_params* p, float* out_field, int* out_dims_host, const int* snap_iters_host, int n_snap,
-                              const int* smooth_host, int n_smooth, void* workspace, size_t workspace_bytes, void* stream) {
+                              const int* smooth_host, int n_smooth, void* workspace, size_t workspace_bytes, void* stream, const LabelPair* labels = nullptr) {
     int rc = validate(p);
     if (rc) return rc;
     const ContextScope scope(p->ctx);           // switches and tables of this call (cvx_pair_params.ctx; nullptr keeps the thread's)
     CVX_REQUIRE(out_field && workspace, "cvx_register_pair_f32: null pointer");
-    if (p->n_feat == 0) CVX_REQUIRE(img_fixed && img_moving, "cvx_register_pair_f32: images missing");
+    if (labels) CVX_REQUIRE(p->n_feat >= 1 && labels->fixed && labels->moving && labels->present && labels->weights,
+                            "cvx_register_label_pair_f32: label maps, channel labels or weights missing, or n_feat == 0 (n_feat = number of channels)");
+    else if (p->n_feat == 0) CVX_REQUIRE(img_fixed && img_moving, "cvx_register_pair_f32: images missing");
     else CVX_REQUIRE(feat_fixed && feat_moving, "cvx_register_pair_f32: feature volumes missing");
     const PairLayout L = pair_layout(*p, n_snap, n_snap ? smooth_max(smooth_host, n_smooth) : 0);
     if (workspace_bytes < L.total) return fail(CVX_ERR_WORKSPACE, "cvx_register_pair_f32: workspace %zu < %zu", workspace_bytes, L.total);
@@ -508,7 +533,7 @@ static int register_pair_core(const float* img_fixed, const float* img_moving, c
     corr_fused_set_prep_hook(g_profiling ? +[](hipStream_t st) { mark("correlate_prep", st); } : nullptr);
     struct HookReset { ~HookReset() { corr_fused_set_prep_hook(nullptr); } } hook_reset;
 
-    PairRun run = {p, L, static_cast<char*>(workspace), s, feat_fixed, feat_moving};
+    PairRun run = {p, L, static_cast<char*>(workspace), s, feat_fixed, feat_moving, labels};
     const bool adam = p->lambda_weight > 0;
     if ((rc = run.features(img_fixed, img_moving))) return rc;
     run.setup();
@@ -539,6 +564,23 @@ extern "C" int cvx_register_pair_f32(const float* img_fixed, const float* img_mo
                                      int* out_dims_host, void* workspace, size_t workspace_bytes, void* stream) {
     return register_pair_core(img_fixed, img_moving, feat_fixed, feat_moving, p, out_field, out_dims_host, nullptr, 0, nullptr, 0, workspace,
                               workspace_bytes, stream);
+}
+
+// ---- label maps in, field out: the pair pipeline with the pooled one-hot features written straight from the maps (labelpool.hip) ----
+// (the pair layout for n_feat = C holds no full-resolution feature buffer, and the label kernel needs no scratch: the same layout function)
+extern "C" size_t cvx_register_label_pair_workspace_bytes(const cvx_pair_params* p) {
+    if (validate(p) != CVX_OK) return 0;
+    if (p->n_feat < 1) { fail(CVX_ERR_INVALID_ARG, "cvx_register_label_pair: n_feat must be the number of channels (>= 1)"); return 0; }
+    const ContextScope scope(p->ctx);
+    return pair_layout(*p).total;
+}
+
+extern "C" int cvx_register_label_pair_f32(const float* lab_fixed, const float* lab_moving, const int* present, const float* weights, float mult,
+                                           const cvx_pair_params* p, float* out_field, int* out_dims_host, void* workspace, size_t workspace_bytes,
+                                           void* stream) {
+    const LabelPair labels = {lab_fixed, lab_moving, present, weights, mult};
+    return register_pair_core(nullptr, nullptr, nullptr, nullptr, p, out_field, out_dims_host, nullptr, 0, nullptr, 0, workspace, workspace_bytes, stream,
+                              &labels);
 }
 
 extern "C" size_t cvx_register_pair_snapshots_workspace_bytes(const cvx_pair_params* p, int n_snap, const int* smooth_host, int n_smooth) {

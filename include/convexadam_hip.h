@@ -189,6 +189,18 @@ int cvx_label_weights_host(const int64_t* hist_fix_host, const int64_t* hist_mov
 int cvx_label_features_f32(const float* lab, int64_t V, int C, const int* present /* device [C] */,
                            const float* weights /* device [C] */, float mult, float* feat, void* stream);
 
+/* label-map features as the registration consumes them -- only through their stride poolings ---------
+ * replaces F.avg_pool3d(extract_features(...), g, stride=g) for the two window sizes of a pair
+ *                                                            convex_adam_nnUNet.py:19-38 + :101-102,117-118
+ *   lab [H][W][D] -> out1 [C][H/g1][W/g1][D/g1]; g2 > 0: out2 [C][H/g2][W/g2][D/g2] as well (out2 NULL iff g2 == 0).  Any pair of windows
+ *   (g2 need not divide g1; g = 1 gives the one-hot volume itself).  Same bits as cvx_label_features_f32 followed by cvx_avgpool_f32: a
+ *   pooled value is the sequential float32 sum of k copies of mult * w_c divided by g^3, k = voxels of the cell with label present[c];
+ *   the [C][H][W][D] one-hot volume is never written and no workspace is needed.  C = 1 .. 255; the entries of `present` are distinct
+ *   (cvx_label_weights_host lists them ascending); a voxel whose label is not listed contributes to no channel. */
+int cvx_label_features_pooled_f32(const float* lab, int H, int W, int D, int C, const int* present /* device [C] */,
+                                  const float* weights /* device [C] */, float mult, int g1, float* out1, int g2 /* 0: none */,
+                                  float* out2 /* NULL iff g2 == 0 */, void* stream);
+
 /* SSD correlation volume ---------------------------------------------------------------------------
  * replaces correlate(mind_fix, mind_mov, disp_hw, grid_sp, shape, ch)   convex_adam_utils.py:72-89
  *   fix, mov [C][h][w][d] (already pooled to the coarse grid)
@@ -402,6 +414,16 @@ size_t cvx_register_pair_workspace_bytes(const cvx_pair_params* p);
 int cvx_register_pair_f32(const float* img_fixed, const float* img_moving, const float* feat_fixed,
                           const float* feat_moving, const cvx_pair_params* p, float* out_field,
                           int* out_dims_host, void* workspace, size_t workspace_bytes, void* stream);
+
+/* the same pipeline from two LABEL MAPS [H][W][D] (convex_adam_nnUNet.py:41-159): p->n_feat = C >= 1 channels with labels present[C] and
+ * weights[C] (device; cvx_label_histogram_i64 + cvx_label_weights_host), features mult * w_c * onehot.  Same field bits as
+ * cvx_label_features_f32 + cvx_register_pair_f32(feat_*), but the pooled features are written straight from the maps
+ * (cvx_label_features_pooled_f32): neither the one-hot volumes nor any buffer of their size exists.  The workspace is the pair's for
+ * the same parameters; stage interval "label_features" instead of "mind". */
+size_t cvx_register_label_pair_workspace_bytes(const cvx_pair_params* p);
+int cvx_register_label_pair_f32(const float* lab_fixed, const float* lab_moving, const int* present /* device [C] */,
+                                const float* weights /* device [C] */, float mult, const cvx_pair_params* p /* n_feat = C >= 1 */,
+                                float* out_field, int* out_dims_host, void* workspace, size_t workspace_bytes, void* stream);
 
 /* the same pipeline with iteration snapshots:
  * replaces the 9-field variant self_configuring/convex_adam_MIND.py:115-139 (disp_sample after iterations 40 / 60 / 80, each without
