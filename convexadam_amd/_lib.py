@@ -50,6 +50,9 @@ class StageParams(C.Structure):
 
 _vp, _i, _f, _sz, _i64 = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_int64
 
+# the arguments every cvx_adam_run_* entry point starts with (F2 .. snapshots); a smoother / mode, then workspace, its size and the stream follow
+_ADAM_HEAD = [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]
+
 # name -> (restype, argtypes); this table is also what tests/test_abi.py checks against the header
 SIGNATURES = {
     "cvx_version": (_i, []),
@@ -101,20 +104,14 @@ SIGNATURES = {
     "cvx_resize_trilinear_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _i, _vp]),
     "cvx_grid_sample_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp]),
     "cvx_adam_workspace_bytes": (_sz, [_i] * 4),
-    "cvx_adam_run_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _i,
-                              _vp, _vp, _sz, _vp]),
+    "cvx_adam_run_f32": (_i, _ADAM_HEAD + [_vp, _sz, _vp]),
     "cvx_smooth_workspace_bytes": (_sz, [_i] * 4),
     "cvx_smooth_f32": (_i, [_vp, _i, _i, _i, _i, C.POINTER(Smoother), _i, _vp, _vp, _sz, _vp]),
-    "cvx_adam_run_smoother_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _i,
-                                       _vp, C.POINTER(Smoother), _vp, _sz, _vp]),
-    "cvx_adam_run_ex_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _i,
-                                 _vp, C.POINTER(Smoother), _i, _vp, _sz, _vp]),
-    "cvx_adam_run_fast_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _i,
-                                   _vp, _vp, _sz, _vp]),
-    "cvx_adam_run_fast_all_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _i,
-                                       _vp, _vp, _sz, _vp]),
-    "cvx_adam_run_mode_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _i,
-                                   _vp, C.POINTER(Smoother), _i, _vp, _sz, _vp]),
+    "cvx_adam_run_smoother_f32": (_i, _ADAM_HEAD + [C.POINTER(Smoother), _vp, _sz, _vp]),
+    "cvx_adam_run_ex_f32": (_i, _ADAM_HEAD + [C.POINTER(Smoother), _i, _vp, _sz, _vp]),
+    "cvx_adam_run_fast_f32": (_i, _ADAM_HEAD + [_vp, _sz, _vp]),
+    "cvx_adam_run_fast_all_f32": (_i, _ADAM_HEAD + [_vp, _sz, _vp]),
+    "cvx_adam_run_mode_f32": (_i, _ADAM_HEAD + [C.POINTER(Smoother), _i, _vp, _sz, _vp]),
     "cvx_smooth_fast_f32": (_i, [_vp, _i, _i, _i, C.POINTER(Smoother), _i, _vp, _vp]),
     "cvx_box3_fast_f32": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "cvx_register_pair_workspace_bytes": (_sz, [C.POINTER(PairParams)]),

@@ -11,6 +11,8 @@
 //   Adam(lr=1, betas=(.9,.999), eps=1e-8): m = fma(.1, g-m, m); v = fma(.001*g, g, v*.999);
 //        P += (-(1/bc1) * m) / (sqrt(v)/sqrt(bc2) + eps)                                   (:179)
 // The loop returns U of the LAST forward pass (:181), i.e. parameters after niter-1 updates.
+// Host side: adam_plan() decides the kernels of a run once -- forward, gradient, adjoint + update (truth table: DESIGN.md 21) -- and
+// adam_run_impl() runs forward_step / gradient_step / update_step per iteration, each one switch over its plan field.
 // Roofline: HBM/L2 -- 185.8 MB algorithmic traffic per iteration at OASIS size; the
 // working set (F2, M2 = 2 x 41 MB) stays resident in the 256 MiB Infinity Cache across iterations.
 #include <math.h>
@@ -78,16 +80,8 @@ __device__ __forceinline__ void box_pass(const float* __restrict__ src, int sy, 
                 if (!BACKWARD) gout[i] = div_exact<27>(sj);
                 else if (!ADAM) gout[i] = sj;
                 else {
-                    const float g = sj;
-                    const float mo = m[i];
-                    const float mm = __builtin_fmaf(ac.w1, g - mo, mo);          // exp_avg.lerp_(grad, 1-beta1)
-                    float vv = v[i] * ac.b2;                                      // exp_avg_sq.mul_(beta2)
-                    vv = __builtin_fmaf(ac.omb2 * g, g, vv);                      // .addcmul_(grad, grad, value=1-beta2)
-                    const float den = fdiv(adam_sqrt(vv, ac.sqrt_tbl), ac.bc2s) + 1e-8f;   // (sqrt / bias_correction2_sqrt).add_(eps)
-                    P[i] = P[i] + fdiv(ac.neg_step * mm, den);                    // addcdiv_(exp_avg, denom, value=-step_size)
-                    m[i] = mm;
-                    v[i] = vv;
-                    if (gsave) gsave[i] = g;
+                    adam_update(sj, P[i], m[i], v[i], ac);
+                    if (gsave) gsave[i] = sj;
                 }
             }
         }
@@ -147,42 +141,56 @@ __global__ __launch_bounds__(256) void k_adam_update(const float* __restrict__ G
                                                      float* __restrict__ v, size_t n, AdamConsts ac) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const float g = G[i];
-    const float mo = m[i];
-    const float mm = __builtin_fmaf(ac.w1, g - mo, mo);          // exp_avg.lerp_(grad, 1-beta1)
-    float vv = v[i] * ac.b2;                                      // exp_avg_sq.mul_(beta2)
-    vv = __builtin_fmaf(ac.omb2 * g, g, vv);                      // .addcmul_(grad, grad, value=1-beta2)
-    const float den = fdiv(adam_sqrt(vv, ac.sqrt_tbl), ac.bc2s) + 1e-8f;   // (sqrt / bias_correction2_sqrt).add_(eps)
-    P[i] = P[i] + fdiv(ac.neg_step * mm, den);                    // addcdiv_(exp_avg, denom, value=-step_size)
-    m[i] = mm;
-    v[i] = vv;
+    adam_update(G[i], P[i], m[i], v[i], ac);
 }
 
-// the k_box3_tile variant (>= 1000) that runs this three-box pass, or 0 (z-marching pipeline / k_box3x3).  adam_run_impl asks it once per
-// iteration for the adjoint, so that the warp kernel pre-divides gU exactly when the tiles take it pre-divided.
-static int box3_tile_choice(const float* in, const float* out, int h, int w, int d, bool backward, const float* P, const float* m, const float* v,
-                            const float* gsave) {
-    if (options().box_tiled != 0) return 0;
-    if (!(backward ? (out || P) && box3_tile_supported(in, out, h, w, d, P, m, v, gsave) : box3_tile_fwd_supported(in, out, h, w, d))) return 0;
-    long long ft = backward ? options().box_bwd_tile : options().box_fwd_tile;
-    if (ft < 0) ft = box3_march_supported(d) ? box3_tile_fwd_auto(h, w, d) : 2000;          // (rows beyond the marching kernel's range: always tiles)
-    return ft >= 1000 ? (int)ft : 0;
-}
-
-// prediv: the adjoint's input is gU / 27 already -- only the tiles take it so (the caller decides with box3_tile_choice)
-static int launch_box3x3(const float* in, float* out, int h, int w, int d, bool backward, float* P, float* m, float* v,
-                         AdamConsts ac, float* gsave, bool prediv, hipStream_t s) {
-    // rows of up to 126 voxels: z-marching pipeline (boxmarch.hip); longer rows: the tiled kernel below
-    const int ft = box3_tile_choice(in, out, h, w, d, backward, P, m, v, gsave);
-    if (ft) return launch_box3_tile(in, out, h, w, d, ft, backward, P, m, v, ac, gsave, prediv, s);
-    if (prediv) return fail(CVX_ERR_INVALID_ARG, "box3x3: pre-divided adjoint taps without the tile kernel");
-    const bool force_tiled = options().box_tiled != 0;
-    if (!force_tiled && box3_march_supported(d)) return launch_box3_march(in, out, h, w, d, backward, P, m, v, ac, gsave, s);
+// (the launcher of k_box3x3 alone: which of tiles / marching / this kernel runs a pass is the plan's decision)
+static int launch_box3x3(const float* in, float* out, int h, int w, int d, bool backward, float* P, float* m, float* v, AdamConsts ac,
+                         float* gsave, hipStream_t s) {
     const int nb = cdiv(d, BT_X) * cdiv(w, BT_Y) * cdiv(h, BT_Z) * 3;
     if (!backward) hipLaunchKernelGGL((k_box3x3<false, false>), dim3(nb), dim3(BT_NT), 0, s, in, out, h, w, d, P, m, v, ac, gsave);
     else if (!P) hipLaunchKernelGGL((k_box3x3<true, false>), dim3(nb), dim3(BT_NT), 0, s, in, out, h, w, d, P, m, v, ac, gsave);
     else hipLaunchKernelGGL((k_box3x3<true, true>), dim3(nb), dim3(BT_NT), 0, s, in, out, h, w, d, P, m, v, ac, gsave);
     return check_last("box3x3");
+}
+
+// ---- which kernels run one iteration: decided once per run (truth table: DESIGN.md 21) --------------------------------------------------
+// Tile / March / Lds = the exact three-box pass on k_box3_tile (boxtile.hip), k_box3_march (boxmarch.hip), k_box3x3 (above)
+enum class AdamFwd { Tile, March, Lds, FastBox3, FastChain, Smoother };
+enum class AdamGrad { Exact, Fast };
+enum class AdamAdj { Tile, March, Lds, FastBox3, FastChainUpdate, SmootherFastUpdate, SmootherUpdate };
+// prediv: k_warp_grad stores gU / 27 and the adjoint tiles take their taps so -- one field, so the two launches cannot disagree
+struct AdamPlan { AdamFwd fwd; int fwd_variant; AdamGrad grad; bool prediv; AdamAdj adj; int adj_variant; };
+
+// the k_box3_tile variant (>= 1000) that runs the exact forward (U = box(P)) or adjoint (box^T(gU) + update of P, m, v, gradient copy
+// into gsave) pass of this run, or 0 = no tiles.  The tiles issue 16-byte accesses: every pointer of the pass takes part.
+static int box3_tile_choice(const Options& o, const AdamRun& r, bool backward, const float* gU, const float* gsave) {
+    if (o.box_tiled != 0) return 0;
+    if (!(backward ? r.P && box3_tile_supported(gU, nullptr, r.h, r.w, r.d, r.P, r.m, r.v, gsave) : box3_tile_fwd_supported(r.P, r.U, r.h, r.w, r.d))) return 0;
+    long long ft = backward ? o.box_bwd_tile : o.box_fwd_tile;
+    if (ft < 0) ft = box3_march_supported(r.d) ? box3_tile_fwd_auto(r.h, r.w, r.d) : 2000;          // (rows beyond the marching kernel's range: always tiles)
+    return ft >= 1000 ? (int)ft : 0;
+}
+
+// packaged: the smoother is the chain of three 3^3 boxes; gsave: where the adjoint of the planned iteration copies the gradient (nullptr:
+// nowhere) -- its alignment decides with the others whether that iteration's adjoint can run on tiles
+static AdamPlan adam_plan(const AdamRun& r, bool packaged, const float* gU, const float* gsave) {
+    const Options& o = options();
+    const bool chain = !packaged && r.sm->kind == 0;
+    const bool march = o.box_tiled == 0 && box3_march_supported(r.d);          // rows of up to 126 voxels; longer rows without tiles: k_box3x3
+    auto box3 = [&](bool backward, auto& kernel, int& variant) {
+        using Kernel = std::decay_t<decltype(kernel)>;
+        variant = box3_tile_choice(o, r, backward, gU, gsave);
+        kernel = variant ? Kernel::Tile : march ? Kernel::March : Kernel::Lds;
+    };
+    AdamPlan p = {AdamFwd::Smoother, 0, r.fast ? AdamGrad::Fast : AdamGrad::Exact, false, AdamAdj::SmootherUpdate, 0};
+    if (r.fast == 2 && packaged) p.fwd = AdamFwd::FastBox3;                    // "fast_all": separable forward boxes too
+    else if (r.fast == 2 && chain) p.fwd = AdamFwd::FastChain;                 // ... for a box chain of the sweep
+    else if (packaged) box3(false, p.fwd, p.fwd_variant);
+    if (r.fast) p.adj = packaged ? AdamAdj::FastBox3 : chain ? AdamAdj::FastChainUpdate : AdamAdj::SmootherFastUpdate;
+    else if (packaged) box3(true, p.adj, p.adj_variant);
+    p.prediv = p.adj == AdamAdj::Tile && o.box_prediv != 0;
+    return p;
 }
 
 }  // namespace cvx
@@ -201,50 +209,32 @@ static AdamWs adam_layout(Carver& cv, int C, size_t V) {
 
 extern "C" size_t cvx_adam_workspace_bytes(int C, int h, int w, int d) { Carver m; adam_layout(m, C, (size_t)h * w * d); return ws_query(m); }
 
-extern "C" int cvx_adam_run_f32(const float* F2, const float* M2, int C, int h, int w, int d, float* P, float* m, float* v,
-                                float lambda_weight, int niter, int step0, float cost_scale, const float* base_h,
-                                const float* base_w, const float* base_d, float* U, float* grad_out,
-                                const int* snapshot_iters_host, int n_snap, float* snapshots, void* workspace,
-                                size_t workspace_bytes, void* stream) {
-    return cvx_adam_run_smoother_f32(F2, M2, C, h, w, d, P, m, v, lambda_weight, niter, step0, cost_scale, base_h, base_w, base_d, U,
-                                     grad_out, snapshot_iters_host, n_snap, snapshots, nullptr, workspace, workspace_bytes, stream);
-}
+// the 24 arguments that every cvx_adam_run_* entry point shares (include/convexadam_hip.h spells them out; a smoother or mode argument sits
+// between the two parameter runs), and the same by name into an AdamRun
+#define ADAM_ABI_HEAD                                                                                                                       \
+    const float *F2, const float *M2, int C, int h, int w, int d, float *P, float *m, float *v, float lambda_weight, int niter, int step0,  \
+    float cost_scale, const float *base_h, const float *base_w, const float *base_d, float *U, float *grad_out,                             \
+    const int *snapshot_iters_host, int n_snap, float *snapshots
+#define ADAM_ABI_TAIL void *workspace, size_t workspace_bytes, void *stream
+#define ADAM_ABI_ARGS                                                                                                                       \
+    .F2 = F2, .M2 = M2, .C = C, .h = h, .w = w, .d = d, .P = P, .m = m, .v = v, .lambda_weight = lambda_weight, .niter = niter, .step0 = step0, \
+    .cost_scale = cost_scale, .base_h = base_h, .base_w = base_w, .base_d = base_d, .U = U, .grad_out = grad_out,                           \
+    .snapshot_iters_host = snapshot_iters_host, .n_snap = n_snap, .snapshots = snapshots, .workspace = workspace,                           \
+    .workspace_bytes = workspace_bytes, .stream = stream
 
-extern "C" int cvx_adam_run_smoother_f32(const float* F2, const float* M2, int C, int h, int w, int d, float* P, float* m, float* v,
-                                         float lambda_weight, int niter, int step0, float cost_scale, const float* base_h,
-                                         const float* base_w, const float* base_d, float* U, float* grad_out,
-                                         const int* snapshot_iters_host, int n_snap, float* snapshots, const cvx_smoother* sm,
-                                         void* workspace, size_t workspace_bytes, void* stream) {
-    return cvx::adam_run_impl(F2, M2, C, h, w, d, P, m, v, lambda_weight, niter, step0, cost_scale, base_h, base_w, base_d, U, grad_out,
-                              snapshot_iters_host, n_snap, snapshots, sm, true, false, 0, workspace, workspace_bytes, stream);
-}
+extern "C" int cvx_adam_run_f32(ADAM_ABI_HEAD, ADAM_ABI_TAIL) { return cvx::adam_run_impl({ADAM_ABI_ARGS}); }
+extern "C" int cvx_adam_run_smoother_f32(ADAM_ABI_HEAD, const cvx_smoother* sm, ADAM_ABI_TAIL) { return cvx::adam_run_impl({ADAM_ABI_ARGS, .sm = sm}); }
+extern "C" int cvx_adam_run_fast_f32(ADAM_ABI_HEAD, ADAM_ABI_TAIL) { return cvx::adam_run_impl({ADAM_ABI_ARGS, .fast = 1}); }
+extern "C" int cvx_adam_run_fast_all_f32(ADAM_ABI_HEAD, ADAM_ABI_TAIL) { return cvx::adam_run_impl({ADAM_ABI_ARGS, .fast = 2}); }
 
-extern "C" int cvx_adam_run_fast_f32(const float* F2, const float* M2, int C, int h, int w, int d, float* P, float* m, float* v,
-                                     float lambda_weight, int niter, int step0, float cost_scale, const float* base_h,
-                                     const float* base_w, const float* base_d, float* U, float* grad_out,
-                                     const int* snapshot_iters_host, int n_snap, float* snapshots, void* workspace,
-                                     size_t workspace_bytes, void* stream) {
-    return cvx::adam_run_impl(F2, M2, C, h, w, d, P, m, v, lambda_weight, niter, step0, cost_scale, base_h, base_w, base_d, U, grad_out,
-                              snapshot_iters_host, n_snap, snapshots, nullptr, true, false, 1, workspace, workspace_bytes, stream);
-}
-
-extern "C" int cvx_adam_run_fast_all_f32(const float* F2, const float* M2, int C, int h, int w, int d, float* P, float* m, float* v,
-                                         float lambda_weight, int niter, int step0, float cost_scale, const float* base_h,
-                                         const float* base_w, const float* base_d, float* U, float* grad_out,
-                                         const int* snapshot_iters_host, int n_snap, float* snapshots, void* workspace,
-                                         size_t workspace_bytes, void* stream) {
-    return cvx::adam_run_impl(F2, M2, C, h, w, d, P, m, v, lambda_weight, niter, step0, cost_scale, base_h, base_w, base_d, U, grad_out,
-                              snapshot_iters_host, n_snap, snapshots, nullptr, true, false, 2, workspace, workspace_bytes, stream);
-}
-
-extern "C" int cvx_adam_run_mode_f32(const float* F2, const float* M2, int C, int h, int w, int d, float* P, float* m, float* v,
-                                     float lambda_weight, int niter, int step0, float cost_scale, const float* base_h,
-                                     const float* base_w, const float* base_d, float* U, float* grad_out,
-                                     const int* snapshot_iters_host, int n_snap, float* snapshots, const cvx_smoother* sm, int mode,
-                                     void* workspace, size_t workspace_bytes, void* stream) {
+extern "C" int cvx_adam_run_mode_f32(ADAM_ABI_HEAD, const cvx_smoother* sm, int mode, ADAM_ABI_TAIL) {
     CVX_REQUIRE((mode & ~16) >= 0 && (mode & ~16) <= 2, "cvx_adam_run_mode_f32: mode must be 0 (exact), 1 (fast) or 2 (fast_all), + 16 for half-precision feature records");
-    return cvx::adam_run_impl(F2, M2, C, h, w, d, P, m, v, lambda_weight, niter, step0, cost_scale, base_h, base_w, base_d, U, grad_out,
-                              snapshot_iters_host, n_snap, snapshots, sm, true, (mode & 16) != 0, mode & 3, workspace, workspace_bytes, stream);
+    return cvx::adam_run_impl({ADAM_ABI_ARGS, .sm = sm, .f16_features = (mode & 16) != 0, .fast = mode & 3});
+}
+
+extern "C" int cvx_adam_run_ex_f32(ADAM_ABI_HEAD, const cvx_smoother* sm, int feature_storage, ADAM_ABI_TAIL) {
+    CVX_REQUIRE(feature_storage == 0 || feature_storage == 1, "cvx_adam_run_ex_f32: feature_storage must be 0 (float32) or 1 (fp16)");
+    return cvx::adam_run_impl({ADAM_ABI_ARGS, .sm = sm, .f16_features = feature_storage == 1});
 }
 
 extern "C" int cvx_smooth_fast_f32(const float* in, int h, int w, int d, const cvx_smoother* sm, int backward, float* out, void* stream) {
@@ -258,35 +248,25 @@ extern "C" int cvx_box3_fast_f32(const float* in, int h, int w, int d, float* ou
     return cvx::launch_box3_fast(in, out, h, w, d, nullptr, nullptr, nullptr, 1.0, 1.0, nullptr, as_stream(stream));
 }
 
-extern "C" int cvx_adam_run_ex_f32(const float* F2, const float* M2, int C, int h, int w, int d, float* P, float* m, float* v,
-                                   float lambda_weight, int niter, int step0, float cost_scale, const float* base_h,
-                                   const float* base_w, const float* base_d, float* U, float* grad_out,
-                                   const int* snapshot_iters_host, int n_snap, float* snapshots, const cvx_smoother* sm,
-                                   int feature_storage, void* workspace, size_t workspace_bytes, void* stream) {
-    CVX_REQUIRE(feature_storage == 0 || feature_storage == 1, "cvx_adam_run_ex_f32: feature_storage must be 0 (float32) or 1 (fp16)");
-    return cvx::adam_run_impl(F2, M2, C, h, w, d, P, m, v, lambda_weight, niter, step0, cost_scale, base_h, base_w, base_d, U, grad_out,
-                              snapshot_iters_host, n_snap, snapshots, sm, true, feature_storage == 1, 0, workspace, workspace_bytes, stream);
-}
-
 // keep_state = false (whole-pair pipeline): P, m, v are scratch there and the result is U of the LAST forward pass
 // (convex_adam_MIND.py:181), so the gradient and the Adam step of the final iteration are never observed and are skipped.
-int cvx::adam_run_impl(const float* F2, const float* M2, int C, int h, int w, int d, float* P, float* m, float* v,
-                       float lambda_weight, int niter, int step0, float cost_scale, const float* base_h, const float* base_w,
-                       const float* base_d, float* U, float* grad_out, const int* snapshot_iters_host, int n_snap,
-                       float* snapshots, const cvx_smoother* sm, bool keep_state, bool f16_features, int fast, void* workspace,
-                       size_t workspace_bytes, void* stream, bool features_are_records) {
-    CVX_REQUIRE(F2 && M2 && P && m && v && U && base_h && base_w && base_d, "cvx_adam_run_f32: null pointer");
+int cvx::adam_run_impl(const AdamRun& r) {
+    const int C = r.C, h = r.h, w = r.w, d = r.d;
+    float *const P = r.P, *const m = r.m, *const v = r.v, *const U = r.U;
+    const cvx_smoother* const sm = r.sm;                                // nullptr: the packaged smoother
+    CVX_REQUIRE(r.F2 && r.M2 && P && m && v && U && r.base_h && r.base_w && r.base_d, "cvx_adam_run_f32: null pointer");
     CVX_REQUIRE(C > 0 && h > 1 && w > 1 && d > 1, "cvx_adam_run_f32: bad extent C=%d %dx%dx%d", C, h, w, d);
-    CVX_REQUIRE(niter >= 0 && step0 >= 0, "cvx_adam_run_f32: negative iteration count");
-    CVX_REQUIRE(n_snap == 0 || (snapshot_iters_host && snapshots), "cvx_adam_run_f32: snapshot buffers missing");
-    if (!workspace || workspace_bytes < cvx_adam_workspace_bytes(C, h, w, d))
-        return fail(CVX_ERR_WORKSPACE, "cvx_adam_run_f32: workspace too small");
-    hipStream_t s = as_stream(stream);
+    CVX_REQUIRE(r.niter >= 0 && r.step0 >= 0, "cvx_adam_run_f32: negative iteration count");
+    CVX_REQUIRE(r.n_snap == 0 || (r.snapshot_iters_host && r.snapshots), "cvx_adam_run_f32: snapshot buffers missing");
+    if (!r.workspace || r.workspace_bytes < cvx_adam_workspace_bytes(C, h, w, d)) return fail(CVX_ERR_WORKSPACE, "cvx_adam_run_f32: workspace too small");
+    hipStream_t s = as_stream(r.stream);
     const size_t V = (size_t)h * w * d;
-    Carver cv(workspace);
-    auto [gU, t1, t2, Fcl, Mcl] = adam_layout(cv, C, V);
+    Carver cv(r.workspace);
+    const AdamWs a = adam_layout(cv, C, V);
+    float *const gU = a.gU, *const t1 = a.t1, *const t2 = a.t2;
+    const float *Fcl = a.Fcl, *Mcl = a.Mcl;                             // the loop's feature records
     // generic smoother path unless it is the packaged chain of three 3^3 boxes (fused LDS kernels)
-    const bool fused = !sm || (sm->kind == 0 && sm->n_boxes == 3 && sm->box_k[0] == 3 && sm->box_k[1] == 3 && sm->box_k[2] == 3);
+    const bool packaged = !sm || (sm->kind == 0 && sm->n_boxes == 3 && sm->box_k[0] == 3 && sm->box_k[1] == 3 && sm->box_k[2] == 3);
     if (sm) {
         CVX_REQUIRE(sm->kind == 0 || sm->kind == 1, "cvx_adam_run_smoother_f32: smoother kind must be 0 or 1");
         if (sm->kind == 0) {
@@ -294,62 +274,81 @@ int cvx::adam_run_impl(const float* F2, const float* M2, int C, int h, int w, in
             for (int i = 0; i < sm->n_boxes; ++i) CVX_REQUIRE(sm->box_k[i] >= 1 && (sm->box_k[i] & 1), "cvx_adam_run_smoother_f32: box size must be odd");
         }
     }
-    if (fast && !fused && sm->kind == 0 && !boxchain_fast_supported(*sm, h, w, d))
+    if (r.fast && !packaged && sm->kind == 0 && !boxchain_fast_supported(*sm, h, w, d))
         return fail(CVX_ERR_UNSUPPORTED, "adam_mode fast: box chain outside the separable kernel's range (odd sizes <= 9, lines of at most 320 voxels)");
-    if (features_are_records) { Fcl = const_cast<float*>(F2); Mcl = const_cast<float*>(M2); }       // built by the producer (mind.hip::k_mind_finish_pool)
-    else if (niter > 0) {
+    if (r.features_are_records) { Fcl = r.F2; Mcl = r.M2; }            // built by the producer (mind.hip::k_mind_finish_pool)
+    else if (r.niter > 0) {
         int rc;
-        if ((rc = launch_to_chunked(F2, C, V, Fcl, f16_features, s)) || (rc = launch_to_chunked(M2, C, V, Mcl, f16_features, s))) return rc;
+        if ((rc = launch_to_chunked(r.F2, C, V, a.Fcl, r.f16_features, s)) || (rc = launch_to_chunked(r.M2, C, V, a.Mcl, r.f16_features, s))) return rc;
     }
 
     // MeanBackward of lambda*mean(diff^2): lambda / N_axis in float32                       (:167-169)
-    const float nH = (float)((int64_t)3 * (h - 1) * w * d), nW = (float)((int64_t)3 * h * (w - 1) * d),
-                nD = (float)((int64_t)3 * h * w * (d - 1));
-    const float cH = lambda_weight / nH, cW = lambda_weight / nW, cD = lambda_weight / nD;
-    const float gsc = ((1.0f / (float)V) * cost_scale) / (float)C;     // MeanBackward, MulBackward, MeanBackward
+    const float nH = (float)((int64_t)3 * (h - 1) * w * d), nW = (float)((int64_t)3 * h * (w - 1) * d), nD = (float)((int64_t)3 * h * w * (d - 1));
+    const float cH = r.lambda_weight / nH, cW = r.lambda_weight / nW, cD = r.lambda_weight / nD;
+    const float gsc = ((1.0f / (float)V) * r.cost_scale) / (float)C;     // MeanBackward, MulBackward, MeanBackward
+    // two plans at most: the iterations that keep no gradient, and the last one when it copies its gradient to grad_out (a misaligned
+    // grad_out takes that iteration's adjoint off the tiles, and its warp kernel off the pre-division with it)
+    const AdamPlan plan = adam_plan(r, packaged, gU, nullptr), plan_save = r.grad_out ? adam_plan(r, packaged, gU, r.grad_out) : plan;
+    const unsigned* const sqrt_tbl = adam_sqrt_table();
+    AdamConsts ac; double bc1, bc2;        // Adam constants and bias corrections 1 - beta^step of the current iteration
+
+    auto forward_step = [&]() -> int {     // U = smooth(P)
+        switch (plan.fwd) {
+        case AdamFwd::Tile:      return launch_box3_tile(P, U, h, w, d, plan.fwd_variant, false, nullptr, nullptr, nullptr, ac, nullptr, false, s);
+        case AdamFwd::March:     return launch_box3_march(P, U, h, w, d, false, nullptr, nullptr, nullptr, ac, nullptr, s);
+        case AdamFwd::Lds:       return launch_box3x3(P, U, h, w, d, false, nullptr, nullptr, nullptr, ac, nullptr, s);
+        case AdamFwd::FastBox3:  return launch_box3_fast(P, U, h, w, d, nullptr, nullptr, nullptr, 1.0, 1.0, nullptr, s);
+        case AdamFwd::FastChain: return launch_boxchain_fast(P, U, h, w, d, *sm, false, s);
+        case AdamFwd::Smoother:  return launch_smoother(P, U, t1, 3, h, w, d, *sm, false, s);
+        }
+    };
+    auto gradient_step = [&](const AdamPlan& pl) -> int {     // gU = d loss / dU
+        switch (pl.grad) {
+        case AdamGrad::Exact: return launch_warp_grad(Fcl, Mcl, C, h, w, d, U, r.base_h, r.base_w, r.base_d, gsc, cH, cW, cD, gU, r.f16_features, pl.prediv, s);
+        case AdamGrad::Fast:  return launch_warp_grad_fast(Fcl, Mcl, C, h, w, d, U, r.base_h, r.base_w, r.base_d, gsc, cH, cW, cD, gU, r.f16_features, s);
+        }
+    };
+    auto update_step = [&](const AdamPlan& pl, float* gsave) -> int {     // G = smooth^T(gU); Adam update of P, m, v with G; gsave = G
+        int rc = CVX_OK;
+        switch (pl.adj) {                  // the three-box kernels update and copy in their last pass ...
+        case AdamAdj::Tile:     return launch_box3_tile(gU, nullptr, h, w, d, pl.adj_variant, true, P, m, v, ac, gsave, pl.prediv, s);
+        case AdamAdj::March:    return launch_box3_march(gU, nullptr, h, w, d, true, P, m, v, ac, gsave, s);
+        case AdamAdj::Lds:      return launch_box3x3(gU, nullptr, h, w, d, true, P, m, v, ac, gsave, s);
+        case AdamAdj::FastBox3: return launch_box3_fast(gU, nullptr, h, w, d, P, m, v, bc1, bc2, gsave, s);
+        // ... the sweep smoothers leave G in t2: a box chain through the separable passes (adjoint = reversed box order), a Gaussian
+        // through its exact 1-D convolutions; the update as an element-wise kernel
+        case AdamAdj::FastChainUpdate:    rc = launch_boxchain_fast(gU, t2, h, w, d, *sm, true, s); break;
+        case AdamAdj::SmootherFastUpdate:
+        case AdamAdj::SmootherUpdate:     rc = launch_smoother(gU, t2, t1, 3, h, w, d, *sm, true, s); break;
+        }
+        if (rc) return rc;
+        if (pl.adj == AdamAdj::SmootherUpdate) hipLaunchKernelGGL(k_adam_update, dim3((unsigned)cdiv64((int64_t)(3 * V), 256)), dim3(256), 0, s, t2, P, m, v, 3 * V, ac);
+        else if ((rc = launch_adam_update_fast(t2, P, m, v, 3 * V, bc1, bc2, s))) return rc;
+        if (gsave) (void)hipMemcpyAsync(gsave, t2, sizeof(float) * 3 * V, hipMemcpyDeviceToDevice, s);
+        return CVX_OK;
+    };
+
     int snap = 0;
-    for (int it = 0; it < niter; ++it) {
+    for (int it = 0; it < r.niter; ++it) {
         int rc;
-        const int step = step0 + it + 1;
+        const int step = r.step0 + it + 1;
         const double beta1 = 0.9, beta2 = 0.999;
-        const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-        const AdamConsts ac = {(float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)sqrt(bc2), (float)(-(1.0 / bc1)), adam_sqrt_table()};
-        if (fast == 2 && fused) { if ((rc = launch_box3_fast(P, U, h, w, d, nullptr, nullptr, nullptr, 1.0, 1.0, nullptr, s))) return rc; }   // "fast_all": separable forward boxes too
-        else if (fast == 2 && sm->kind == 0) { if ((rc = launch_boxchain_fast(P, U, h, w, d, *sm, false, s))) return rc; }             // ... for a box chain of the sweep
-        else if (fused) { if ((rc = launch_box3x3(P, U, h, w, d, false, nullptr, nullptr, nullptr, ac, nullptr, false, s))) return rc; }
-        else if ((rc = launch_smoother(P, U, t1, 3, h, w, d, *sm, false, s))) return rc;
+        bc1 = 1.0 - pow(beta1, (double)step); bc2 = 1.0 - pow(beta2, (double)step);
+        ac = {(float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)sqrt(bc2), (float)(-(1.0 / bc1)), sqrt_tbl};
+        const bool last = it == r.niter - 1;
+        const bool skip = last && !r.keep_state && !r.grad_out;     // nobody observes the last gradient and update
+        float* const gsave = last ? r.grad_out : nullptr;
+        if ((rc = forward_step())) return rc;
         profile_mark_kernel("adam.forward_boxes", s);
-        const bool last = it == niter - 1;
-        if (!(last && !keep_state && !grad_out)) {
-        float* gsave = (grad_out && it == niter - 1) ? grad_out : nullptr;
-        if (fast) {
-            if ((rc = launch_warp_grad_fast(Fcl, Mcl, C, h, w, d, U, base_h, base_w, base_d, gsc, cH, cW, cD, gU, f16_features, s))) return rc;
+        if (!skip) {
+            const AdamPlan& pl = gsave ? plan_save : plan;
+            if ((rc = gradient_step(pl))) return rc;
             profile_mark_kernel("adam.warp_gradient", s);
-            if (fused) { if ((rc = launch_box3_fast(gU, nullptr, h, w, d, P, m, v, bc1, bc2, gsave, s))) return rc; }
-            else {
-                // sweep smoothers: a box chain through the separable passes (adjoint = reversed box order), a Gaussian through its exact
-                // 1-D convolutions; the update as an element-wise kernel
-                if (sm->kind == 0) { if ((rc = launch_boxchain_fast(gU, t2, h, w, d, *sm, true, s))) return rc; }
-                else if ((rc = launch_smoother(gU, t2, t1, 3, h, w, d, *sm, true, s))) return rc;
-                if ((rc = launch_adam_update_fast(t2, P, m, v, 3 * V, bc1, bc2, s))) return rc;
-                if (gsave) (void)hipMemcpyAsync(gsave, t2, sizeof(float) * 3 * V, hipMemcpyDeviceToDevice, s);
-            }
-        } else {
-        // one decision for both launches: gU / 27 from the warp kernel exactly when the adjoint runs on the tiles
-        const bool prediv = fused && options().box_prediv != 0 && box3_tile_choice(gU, nullptr, h, w, d, true, P, m, v, gsave) != 0;
-        if ((rc = launch_warp_grad(Fcl, Mcl, C, h, w, d, U, base_h, base_w, base_d, gsc, cH, cW, cD, gU, f16_features, prediv, s))) return rc;
-        profile_mark_kernel("adam.warp_gradient", s);
-        if (fused) { if ((rc = launch_box3x3(gU, nullptr, h, w, d, true, P, m, v, ac, gsave, prediv, s))) return rc; }
-        else {
-            if ((rc = launch_smoother(gU, t2, t1, 3, h, w, d, *sm, true, s))) return rc;
-            hipLaunchKernelGGL(k_adam_update, dim3((unsigned)cdiv64((int64_t)(3 * V), 256)), dim3(256), 0, s, t2, P, m, v, 3 * V, ac);
-            if (gsave) (void)hipMemcpyAsync(gsave, t2, sizeof(float) * 3 * V, hipMemcpyDeviceToDevice, s);
+            if ((rc = update_step(pl, gsave))) return rc;
+            profile_mark_kernel("adam.adjoint_update", s);
         }
-        }
-        }
-        if (!(last && !keep_state && !grad_out)) profile_mark_kernel("adam.adjoint_update", s);
-        while (snap < n_snap && snapshot_iters_host[snap] == it + 1) {
-            (void)hipMemcpyAsync(snapshots + (size_t)snap * 3 * V, U, sizeof(float) * 3 * V, hipMemcpyDeviceToDevice, s);
+        while (snap < r.n_snap && r.snapshot_iters_host[snap] == it + 1) {
+            (void)hipMemcpyAsync(r.snapshots + (size_t)snap * 3 * V, U, sizeof(float) * 3 * V, hipMemcpyDeviceToDevice, s);
             ++snap;
         }
     }

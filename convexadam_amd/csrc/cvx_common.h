@@ -432,13 +432,19 @@ __device__ __forceinline__ void adam_update(float g, float& P, float& m, float& 
     m = mm;
     v = vv;
 }
-// adam.hip: the Adam loop behind cvx_adam_run_f32 / cvx_adam_run_smoother_f32; keep_state = false lets the whole-pair pipeline
-// drop the final (unobserved) gradient + update
-int adam_run_impl(const float* F2, const float* M2, int C, int h, int w, int d, float* P, float* m, float* v, float lambda_weight,
-                  int niter, int step0, float cost_scale, const float* base_h, const float* base_w, const float* base_d, float* U,
-                  float* grad_out, const int* snapshot_iters_host, int n_snap, float* snapshots, const cvx_smoother* sm,
-                  bool keep_state, bool f16_features, int fast, void* workspace, size_t workspace_bytes, void* stream,
-                  bool features_are_records = false);   // fast: 0 exact, 1 fast, 2 fast_all; features_are_records: F2 / M2 already hold the chunked records
+// adam.hip: the Adam loop behind the cvx_adam_run_* entry points and the whole-pair pipeline.  One argument bundle, filled by name: the 24
+// arguments of cvx_adam_run_f32 (include/convexadam_hip.h), then what the callers differ in
+struct AdamRun {
+    const float *F2, *M2; int C, h, w, d; float *P, *m, *v; float lambda_weight; int niter, step0; float cost_scale;
+    const float *base_h, *base_w, *base_d; float *U, *grad_out; const int* snapshot_iters_host; int n_snap; float* snapshots;
+    void* workspace; size_t workspace_bytes; void* stream;
+    const cvx_smoother* sm = nullptr;      // nullptr: the packaged chain of three 3^3 boxes
+    bool keep_state = true;                // false lets the whole-pair pipeline drop the final (unobserved) gradient + update
+    bool f16_features = false;             // the loop's feature records in half precision
+    int fast = 0;                          // 0 exact, 1 fast, 2 fast_all
+    bool features_are_records = false;     // F2 / M2 already hold the chunked records
+};
+int adam_run_impl(const AdamRun& r);
 size_t adam_record_floats(int C, size_t V);            // floats of one feature record of the Adam loop: [CP/4][V + 1][4], CP = C rounded up to 4
 // convex.hip: coupled convex regularisation behind cvx_coupled_convex_f32 (argmin_is_exact: see there)
 int coupled_convex_impl(const void* ssd, bool f16, const int64_t* argmin, const float* mesh, int h, int w, int d, int disp_hw, float* out,

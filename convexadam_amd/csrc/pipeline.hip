@@ -493,10 +493,13 @@ struct PairRun {
         // (fp16 storage: the Adam loop keeps its feature records in half precision -- rounded when the records are built)
         mark("adam_setup", s);
         const cvx_smoother two_pools = {0, 2, {3, 3, 0, 0}, {0.f, 0.f, 0.f, 0.f, 0.f}};            // task3_docker.py:191
-        if ((rc = adam_run_impl(F(L.F2), F(L.M2), L.C, L.h2, L.w2, L.d2, F(L.P), F(L.m), F(L.v_), p->lambda_weight,
-                                p->selected_niter, 0, p->cost_scale, F(L.bh2), F(L.bw2), F(L.bd2), F(L.U), nullptr, snap_iters_host, n_snap,
-                                n_snap ? F(L.snaps) : nullptr, p->n_spline_pools == 2 ? &two_pools : nullptr, /*keep_state=*/false, f16(), p->adam_fast, ws + L.adam_ws,
-                                cvx_adam_workspace_bytes(L.C, L.h2, L.w2, L.d2), s, mind_records))) return rc;
+        if ((rc = adam_run_impl({.F2 = F(L.F2), .M2 = F(L.M2), .C = L.C, .h = L.h2, .w = L.w2, .d = L.d2, .P = F(L.P), .m = F(L.m), .v = F(L.v_),
+                                 .lambda_weight = p->lambda_weight, .niter = p->selected_niter, .step0 = 0, .cost_scale = p->cost_scale,
+                                 .base_h = F(L.bh2), .base_w = F(L.bw2), .base_d = F(L.bd2), .U = F(L.U), .grad_out = nullptr,
+                                 .snapshot_iters_host = snap_iters_host, .n_snap = n_snap, .snapshots = n_snap ? F(L.snaps) : nullptr,
+                                 .workspace = ws + L.adam_ws, .workspace_bytes = cvx_adam_workspace_bytes(L.C, L.h2, L.w2, L.d2), .stream = s,
+                                 .sm = p->n_spline_pools == 2 ? &two_pools : nullptr, .keep_state = false, .f16_features = f16(),
+                                 .fast = p->adam_fast, .features_are_records = mind_records}))) return rc;
         mark("adam", s);
         // disp_hr = interpolate(fitted_grid * grid_sp_adam, (H,W,D))                            (:182)
         if (n_snap > 0) {                       // self_configuring/convex_adam_MIND.py:115-139: every snapshot x every final smoothing

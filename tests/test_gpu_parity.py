@@ -395,6 +395,70 @@ def test_adam_grid_shapes_vs_oracle(U, orc, shape):
     assert np.array_equal(host(st["m"])[0], r["m"]) and np.array_equal(host(st["v"])[0], r["v"])
 
 
+ALIGN_SHAPE, ALIGN_C, ALIGN_NITER = (5, 3, 8), 4, 3
+_align_cache = {}
+
+
+def _alignment_case(orc, mode):
+    """Inputs of the alignment tests and the oracle's result for `mode`, computed once."""
+    if mode not in _align_cache:
+        rng = np.random.default_rng(538)
+        F2 = rng.random((ALIGN_C,) + ALIGN_SHAPE, dtype=np.float32)
+        M2 = rng.random((ALIGN_C,) + ALIGN_SHAPE, dtype=np.float32)
+        P0 = (0.7 * rng.standard_normal((3,) + ALIGN_SHAPE)).astype(np.float32)
+        _align_cache[mode] = F2, M2, P0, orc.adam_run(F2, M2, P0, 1.25, ALIGN_NITER, want_grad=True, mode=mode)
+    return _align_cache[mode]
+
+
+def _adam_run_at_offsets(U, orc, mode, variant):
+    """The Adam loop through ctypes with grad_out, or P, m and v, one float into larger buffers (16-byte aligned + 4 bytes), tiles asked
+    for in both directions: U, G, P, m, v against the oracle, bit for bit."""
+    import ctypes as C
+    from convexadam_amd import _lib
+    L = _lib.lib()
+    F2, M2, P0, r = _alignment_case(orc, mode)
+    h, w, d = ALIGN_SHAPE
+    n = 3 * h * w * d
+
+    def buf(offset):                                               # n floats, `offset` floats behind a 16-byte boundary
+        t = torch.zeros(n + 4, device=DEV)[offset:offset + n]
+        assert t.data_ptr() % 16 == 4 * offset
+        return t
+    state_off, grad_off = {"aligned": (0, 0), "grad_out_offset": (0, 1), "state_offset": (1, 0)}[variant]
+    P, m, v, G, Ud = buf(state_off), buf(state_off), buf(state_off), buf(grad_off), buf(0)
+    P.copy_(dev(P0).reshape(-1))
+    F2d, M2d = dev(F2), dev(M2)
+    bh, bw, bd = U._base_tables(h, w, d, DEV)
+    nws = L.cvx_adam_workspace_bytes(ALIGN_C, h, w, d)
+    ws = _lib.workspace(nws, torch.device(DEV))
+    a = (_lib.ptr(F2d), _lib.ptr(M2d), ALIGN_C, h, w, d, _lib.ptr(P), _lib.ptr(m), _lib.ptr(v), 1.25, ALIGN_NITER, 0, 12.0, _lib.ptr(bh),
+         _lib.ptr(bw), _lib.ptr(bd), _lib.ptr(Ud), _lib.ptr(G), None, 0, None, _lib.ptr(ws), nws, _lib.stream_ptr(torch.device(DEV)))
+    old = L.cvx_get_option(b"box_fwd_tile"), L.cvx_get_option(b"box_bwd_tile")
+    assert L.cvx_set_option(b"box_fwd_tile", 2000) == 0 and L.cvx_set_option(b"box_bwd_tile", 2000) == 0
+    try:
+        _lib.check(L.cvx_adam_run_f32(*a) if mode == "exact" else L.cvx_adam_run_mode_f32(*a[:-3], None, 1, *a[-3:]))
+    finally:
+        L.cvx_set_option(b"box_fwd_tile", old[0]); L.cvx_set_option(b"box_bwd_tile", old[1])
+    for name, t in (("U", Ud), ("G", G), ("P", P), ("m", m), ("v", v)):
+        assert np.array_equal(host(t).reshape((3,) + ALIGN_SHAPE), r[name]), name
+
+
+@pytest.mark.parametrize("variant", ["aligned", "grad_out_offset", "state_offset"])
+def test_adam_gradient_buffer_alignment_vs_oracle(U, orc, variant):
+    """The tile kernels issue 16-byte accesses to every buffer of their pass, so the pointers' alignment takes part in the kernel choice
+    (adam_plan).  5 x 3 x 8 is smaller than one tile in every direction with whole quads per row: all aligned = tiles in
+    every pass; grad_out one float off = the last iteration alone hands its adjoint (and the pre-division of gU) over to the marching
+    kernel; P, m, v one float off = the forward pass and every adjoint on the marching kernel."""
+    _adam_run_at_offsets(U, orc, "exact", variant)
+
+
+@pytest.mark.parametrize("variant", ["aligned", "grad_out_offset", "state_offset"])
+def test_adam_fast_gradient_buffer_alignment_vs_oracle(U, orc, variant):
+    """The same three placements in mode "fast" (exact forward boxes chosen by the plan, the separable adjoint kernel with its own
+    alignment handling behind it) against the oracle's restatement of the fast arithmetic."""
+    _adam_run_at_offsets(U, orc, "fast", variant)
+
+
 @pytest.mark.parametrize("variant", [1000, 2000, 1834, 2274, 1111, 2999])
 @pytest.mark.parametrize("shape", [(13, 9, 8), (5, 3, 4), (12, 8, 56), (25, 17, 60), (24, 16, 116), (2, 2, 4), (14, 31, 52), (30, 20, 112), (4, 8, 132)])
 def test_forward_box_tiles_vs_oracle(U, orc, shape, variant):
