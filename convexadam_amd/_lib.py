@@ -161,6 +161,8 @@ SIGNATURES = {
     "cvx_rigid_samples_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "cvx_convex_stage_workspace_bytes": (_sz, [C.POINTER(StageParams)]),
     "cvx_convex_stage_f32": (_i, [_vp, _vp, _vp, _vp, C.POINTER(StageParams), _vp, _vp, _vp, _sz, _vp]),
+    "cvx_ssim3d_workspace_bytes": (_sz, [_i] * 6),
+    "cvx_ssim3d_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

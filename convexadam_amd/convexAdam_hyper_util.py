@@ -18,6 +18,8 @@ Evaluation operators of that file, on the device:
 plus the three call sequences the sweep scripts write inline (convex_run_withconfig.py:141,148-150,
 convex_run_paired_mind.py:167-173): warp_labels_nearest, jacobian_log_std_and_folding, tre_at_keypoints.
 cupy_hd95(fixed, moving, num_labels, precision=1)    :32-51   (device feature transforms + histogram percentile)
+The label-free measure the reference's own tests accept a result by (tests/helper_functions.py:102-145), from convexadam_amd.ssim:
+    gaussian, create_window_3D, ssim3D(img1, img2, window_size=11, size_average=True), ssim3D_map, registration_ssim(fixed, moving, disp)
 """
 import ctypes as C
 import os
@@ -31,6 +33,7 @@ from .convex_adam_utils import MINDSSC as _MINDSSC
 from .convex_adam_MIND import extract_features as _extract_features
 from .convex_adam_nnUNet import extract_features as _extract_features_nnunet
 from .rigid import find_rigid_3d, least_trimmed_rigid  # noqa: F401  (self_configuring/convexAdam_hyper_util.py:326-346)
+from .ssim import create_window_3D, gaussian, registration_ssim, ssim3D, ssim3D_map  # noqa: F401  (tests/helper_functions.py:102-145)
 
 
 def MINDSSC(img, radius=2, dilation=2):

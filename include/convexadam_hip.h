@@ -621,6 +621,25 @@ size_t cvx_rigid_samples_workspace_bytes(int h, int w, int d, int H, int W, int 
 int cvx_rigid_samples_f32(const float* coarse_field, const unsigned char* mask, int h, int w, int d, int H, int W, int D, float* T1,
                           float* T2, int64_t* count_host, void* workspace, size_t workspace_bytes, void* stream);
 
+/* 3-D structural similarity (csrc/ssim.hip) ----------------------------------------------------------------------------------------
+ * replaces ssim3D / _ssim_3D of tests/helper_functions.py:102-145, the acceptance criterion of tests/test_convex_adam_mind.py:45-85.
+ *   img1, img2 [n][c][h][w][d]; every (n, c) volume is filtered on its own (groups = channel) with the separable Gaussian window of
+ *   window_size taps per axis (sigma 1.5, normalised, zero padding, no renormalisation at the border: F.conv3d(padding = ws / 2)):
+ *       mu1 = G*x, mu2 = G*y, s1 = G*(x x) - mu1 mu1, s2 = G*(y y) - mu2 mu2, s12 = G*(x y) - mu1 mu2,
+ *       ssim = ((2 mu1 mu2 + C1) (2 s12 + C2)) / ((mu1 mu1 + mu2 mu2 + C1) (s1 + s2 + C2)),  C1 = 0.01^2, C2 = 0.03^2
+ *   in float32 with IEEE division; the 1-D weights are computed on the host in float64 and rounded to float32.
+ *   window_size odd, 1 .. 11: an even one is CVX_ERR_INVALID_ARG (it grows the reference's output), a larger one CVX_ERR_UNSUPPORTED.
+ *   Outputs, each produced only when its pointer is not NULL (at least one must be):
+ *     map        [n][c][h][w][d]  the ssim map; must not overlap an input
+ *     mean       one float: the mean over everything (size_average=True)
+ *     slice_mean [n][d]: ssim_map.mean(1).mean(1).mean(1) of the 5-D map (size_average=False), i.e. the mean over c, h and w for
+ *                every index of the LAST axis -- the reference's result as it is, not a per-sample mean
+ *   The means are sums of float64 partials added in a fixed order (no atomics): the same bits on every run.  The workspace holds those
+ *   partials; a call that asks for the map alone takes none (workspace may be NULL). */
+size_t cvx_ssim3d_workspace_bytes(int n, int c, int h, int w, int d, int window_size);
+int cvx_ssim3d_f32(const float* img1, const float* img2, int n, int c, int h, int w, int d, int window_size, float* map, float* mean,
+                   float* slice_mean, void* workspace, size_t workspace_bytes, void* stream);
+
 #pragma GCC visibility pop
 
 #ifdef __cplusplus
