@@ -163,6 +163,8 @@ SIGNATURES = {
     "cvx_convex_stage_f32": (_i, [_vp, _vp, _vp, _vp, C.POINTER(StageParams), _vp, _vp, _vp, _sz, _vp]),
     "cvx_ssim3d_workspace_bytes": (_sz, [_i] * 6),
     "cvx_ssim3d_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "cvx_resample_linear_f64": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, C.c_double, _vp]),
+    "cvx_field_to_grid_f64": (_i, [_vp, _i, _i64, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
 }
 
 _lib = None

@@ -7,7 +7,8 @@
 `astype(float)` exactly as validate_image does (convex_adam_utils.py:268-279) and give a float64 result; tensors keep their dtype
 for the result (integer tensors are rounded to nearest like scipy's integer output arrays).
 apply_convex_original_moving (:27-78): the field is first carried onto the grid, axes and voxel size of the original moving image
-(host-side SimpleITK geometry, convex_adam_utils.rescale_displacement_field), then the warp above runs on the device.
+(host-side SimpleITK geometry, convex_adam_utils.rescale_displacement_field), then the warp above runs on the device; with `device=`
+and built-in images both steps are one kernel launch (geometry.rescale_displacement_field_device).
 """
 import numpy as np
 import torch
@@ -36,10 +37,20 @@ def apply_convex(disp, moving, device=None) -> np.ndarray:
     return out.to(out_dtype).cpu().numpy()
 
 
-def apply_convex_original_moving(disp, moving_image_original, fixed_image_original, fixed_image_resampled):
+def apply_convex_original_moving(disp, moving_image_original, fixed_image_original, fixed_image_resampled, device=None):
     """Warp the ORIGINAL moving image (its own grid, orientation and spacing) with a field estimated on the resampled fixed grid
-    (apply_convex.py:27-78): images in (SimpleITK, or convexadam_amd.imageio.Image), float32 image with the moving image's geometry out."""
+    (apply_convex.py:27-78): images in (SimpleITK, or convexadam_amd.imageio.Image), float32 image with the moving image's geometry out.
+    device: None = the field is carried on the host and uploaded for the warp; a HIP device = built-in images through ONE launch that
+    carries the field and warps (csrc/geometry.hip), nothing but the field and the image going up and the warped voxels coming back."""
     from .imageio import Image
+    if device is not None and isinstance(moving_image_original, Image):
+        from . import geometry
+        field = validate_image(disp).to(device)
+        warped = geometry.rescale_displacement_field_device(field, moving_image_original, fixed_image_original, fixed_image_resampled,
+                                                            moving=validate_image(moving_image_original).to(device), want_field=False)
+        out = Image(warped.cpu().numpy())
+        out.CopyInformation(moving_image_original)
+        return out
     field = validate_image(disp).cpu().numpy()
     field = rescale_displacement_field(field, moving_image_original, fixed_image_original, fixed_image_resampled)
     warped = apply_convex(disp=field, moving=moving_image_original)

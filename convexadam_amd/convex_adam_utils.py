@@ -385,11 +385,12 @@ def validate_image(img, dtype=float):
     return img
 
 
-# ---- geometry helpers around the registration (host side; convex_adam_utils.py:282-351) -----------------------------------------
-# Kept importable under the reference's names (tests/test_convex_adam_mind_aniso.py:10-12, convex_adam_translation.py:9).  Geometry
-# glue, no device work.  SimpleITK images go through SimpleITK's resampler exactly as in the reference; `imageio.Image` objects (the
-# built-in image class, used when SimpleITK is not installed or simply not wanted) go through imageio.resample, which follows ITK's
-# index -> physical-point convention and linear interpolation.
+# ---- geometry helpers around the registration (convex_adam_utils.py:282-351) -----------------------------------------------------
+# Kept importable under the reference's names (tests/test_convex_adam_mind_aniso.py:10-12, convex_adam_translation.py:9).  SimpleITK
+# images go through SimpleITK's resampler exactly as in the reference; `imageio.Image` objects (the built-in image class, used when
+# SimpleITK is not installed or simply not wanted) go through imageio.resample on the host, which follows ITK's index -> physical-point
+# convention and linear interpolation -- or, with `device=` given, through the kernels of csrc/geometry.hip (geometry.py), which
+# restate the same arithmetic in float64 and return the same types.
 def _sitk():
     try:
         import SimpleITK as sitk  # noqa: N813
@@ -416,28 +417,40 @@ def _linear_resampler(sitk, spacing, size, direction, origin):
     return r
 
 
-def _resample(img, spacing, size, direction, origin):
+def _resample(img, spacing, size, direction, origin, device=None):
     if _is_builtin(img):
+        if device is not None:
+            from . import geometry
+            from .imageio import Image
+            out_grid = geometry.Grid(tuple(int(v) for v in size), tuple(spacing), tuple(origin), tuple(direction))
+            out = geometry.resample_device(geometry.upload(img, device), geometry.grid_of(img), out_grid)
+            return Image(out.cpu().numpy().astype(img.array.dtype, copy=False), spacing, origin, direction)
         from .imageio import resample
         return resample(img, spacing, size, direction, origin)
     return _linear_resampler(_sitk(), spacing, size, direction, origin).Execute(img)
 
 
-def resample_img(img, spacing):
-    """Linear resampling of an image to `spacing` on its own origin / orientation; size = floor(n * old / new + 0.5)."""
+def resample_img(img, spacing, device=None):
+    """Linear resampling of an image to `spacing` on its own origin / orientation; size = floor(n * old / new + 0.5).
+    device: None = on the host; a HIP device = built-in images through the resampling kernel (same type and geometry out)."""
     size = [int(n * old / new + 0.5) for n, old, new in zip(img.GetSize(), img.GetSpacing(), spacing)]
-    return _resample(img, spacing, size, img.GetDirection(), img.GetOrigin())
+    return _resample(img, spacing, size, img.GetDirection(), img.GetOrigin(), device)
 
 
-def resample_moving_to_fixed(fixed, moving):
-    """Linear resampling of `moving` onto the voxel grid of `fixed` (zero outside)."""
-    return _resample(moving, fixed.GetSpacing(), fixed.GetSize(), fixed.GetDirection(), fixed.GetOrigin())
+def resample_moving_to_fixed(fixed, moving, device=None):
+    """Linear resampling of `moving` onto the voxel grid of `fixed` (zero outside); device as for resample_img."""
+    return _resample(moving, fixed.GetSpacing(), fixed.GetSize(), fixed.GetDirection(), fixed.GetOrigin(), device)
 
 
-def rescale_displacement_field(displacement_field, moving_image, fixed_image, fixed_image_resampled):
+def rescale_displacement_field(displacement_field, moving_image, fixed_image, fixed_image_resampled, device=None):
     """Displacement field (H,W,D,3; components z,y,x in voxels of `fixed_image_resampled`) -> the grid, axes and voxel size of the
     original `moving_image`: every component is resampled onto the moving grid, the vectors are rotated by the rotation between
-    the two direction-cosine frames and scaled by the spacing ratio."""
+    the two direction-cosine frames and scaled by the spacing ratio.
+    device: None = on the host; a HIP device = built-in images through one launch of the carry-over kernel (float64 array out)."""
+    if device is not None and _is_builtin(moving_image):
+        from . import geometry
+        field = displacement_field if isinstance(displacement_field, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(displacement_field))
+        return geometry.rescale_displacement_field_device(field.to(device), moving_image, fixed_image, fixed_image_resampled).cpu().numpy()
     field = np.asarray(displacement_field)
     comps = []
     if _is_builtin(moving_image):
@@ -476,3 +489,6 @@ from .tps import TPS, thin_plate_dense, tps_densify  # noqa: E402,F401
 from .rigid import affine_warp, find_rigid_3d, least_trimmed_rigid, rigid_from_field  # noqa: E402,F401
 # the script's coarse foreground mask and landmark score (l2r_2020_convexAdam_CuRIOUS.py:312-319,328-330): csrc/rigidreg.hip
 from .rigid import convex_adam_rigid, convex_stage, label_centroids, landmark_tre, rigid_samples, threshold_pool_mask  # noqa: E402,F401
+# physical-space resampling and field carry-over on the device (convex_adam_utils.py:282-351, apply_convex.py:27-78): csrc/geometry.hip
+from .geometry import (Grid, grid_of, index_map, register_images, resample_device,  # noqa: E402,F401
+                       rescale_displacement_field_device)

@@ -12,6 +12,7 @@
 #include <math.h>
 
 #include "cvx_common.h"
+#include "interp_f64.h"
 
 namespace cvx {
 
@@ -121,23 +122,7 @@ __global__ __launch_bounds__(256) void k_map_linear_f64(const double* __restrict
     if (p >= V) return;
     const int x = (int)(p % D), y = (int)((p / D) % W), z = (int)(p / ((size_t)D * W));
     const double cz = disp[3 * p] + (double)z, cy = disp[3 * p + 1] + (double)y, cx = disp[3 * p + 2] + (double)x;
-    double r = 0.0;
-    if (cz >= 0.0 && cz <= (double)(H - 1) && cy >= 0.0 && cy <= (double)(W - 1) && cx >= 0.0 && cx <= (double)(D - 1)) {
-        const double fz = floor(cz), fy = floor(cy), fx = floor(cx);
-        const double tz = cz - fz, ty = cy - fy, tx = cx - fx;
-        const int z0 = (int)fz, y0 = (int)fy, x0 = (int)fx;
-        const int z1 = z0 + 1 < H ? z0 + 1 : H - 1, y1 = y0 + 1 < W ? y0 + 1 : W - 1, x1 = x0 + 1 < D ? x0 + 1 : D - 1;
-        const int zz[2] = {z0, z1}, yy[2] = {y0, y1}, xx[2] = {x0, x1};
-        // scipy completes the spline weights so that they sum to exactly one: w1 = 1 - w0 (not t)
-        const double wz[2] = {1.0 - tz, 1.0 - (1.0 - tz)}, wy[2] = {1.0 - ty, 1.0 - (1.0 - ty)}, wx[2] = {1.0 - tx, 1.0 - (1.0 - tx)};
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int k = 0; k < 2; ++k) r += ((mov[((size_t)zz[i] * W + yy[j]) * D + xx[k]] * wz[i]) * wy[j]) * wx[k];
-    }
-    out[p] = r;
+    out[p] = map_linear_f64(mov, 1, H, W, D, cz, cy, cx);             // interp_f64.h (shared with geometry.hip)
 }
 
 }  // namespace cvx

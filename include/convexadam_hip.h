@@ -640,6 +640,32 @@ size_t cvx_ssim3d_workspace_bytes(int n, int c, int h, int w, int d, int window_
 int cvx_ssim3d_f32(const float* img1, const float* img2, int n, int c, int h, int w, int d, int window_size, float* map, float* mean,
                    float* slice_mean, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Physical-space resampling and field carry-over (csrc/geometry.hip) ------------------------------------------------------------------
+ * replaces SimpleITK's resampler around the registration: resample_img / resample_moving_to_fixed / rescale_displacement_field of
+ * src/convexAdam/convex_adam_utils.py:282-351 and apply_convex_original_moving of src/convexAdam/apply_convex.py:27-78.
+ * Volumes are [z][y][x] (x fastest) of float (flag 0) or double (flag 1).  map12_host (HOST, 12 doubles M[3][3], t[3]) maps an OUTPUT
+ * index to a SOURCE index: (x, y, z)_src = M . (x, y, z)_out + t, evaluated per axis as ((M0 i + M1 j) + M2 k) + t in float64 with plain
+ * multiplies and adds.  A source coordinate is inside when -0.5 <= c <= n - 0.5 on all three axes (ITK's buffer rule; decided before any
+ * conversion to an integer, so a non-finite coordinate is outside); inside, c is clamped to [0, n - 1] and the value is the sum over the 8
+ * taps (z slowest) of ((v * wz) * wy) * wx with weights {1 - t, 1 - (1 - t)}, started from 0.0 -- scipy's map_coordinates(order=1).
+ *   cvx_resample_linear_f64 : out[oz][oy][ox] = that value, or default_value outside; a float output is the round-to-nearest cast.
+ *   cvx_field_to_grid_f64   : field = displacement on the resampled fixed grid [fz][fy][fx], component c (0, 1, 2 = along z, y, x; voxels)
+ *                             of voxel q at field[c * comp_stride + q * voxel_stride] (elements): strides (1, 3) = [fz][fy][fx][3] as
+ *                             convex_adam_pt returns it, (fz fy fx, 1) = [3][fz][fy][fx] as cvx_register_pair_f32 does.  Per voxel of the
+ *                             moving grid [mz][my][mx]: (vz, vy, vx) = the components resampled as above (default 0), rot_b = ((vx R[0][b]
+ *                             + vy R[1][b]) + vz R[2][b]), s_b = rot_b * ratio[b] with rot9_host = inv(D_fixed) D_moving and ratio3_host =
+ *                             spacing of the field's grid / spacing of the moving grid, both HOST, x, y, z order.
+ *                             carried [mz][my][mx][3] float64 = (s_z, s_y, s_x); warped [mz][my][mx] = moving sampled at (z + s_z,
+ *                             y + s_y, x + s_x) exactly as cvx_map_coordinates_linear_f64 does (0 unless 0 <= c <= n - 1 on every axis).
+ *                             Either output may be NULL, not both; warped needs moving.
+ * CVX_ERR_INVALID_ARG before anything is launched: NULL or overlapping buffers, an extent below 1, a volume of more than 2^31 - 1 voxels,
+ * a non-finite entry in a host array or in default_value, strides that fold the components onto each other.  No workspace, no atomics. */
+int cvx_resample_linear_f64(const void* src, int src_f64, int sz, int sy, int sx, void* out, int out_f64, int oz, int oy, int ox,
+                            const double* map12_host, double default_value, void* stream);
+int cvx_field_to_grid_f64(const void* field, int field_f64, int64_t comp_stride, int64_t voxel_stride, int fz, int fy, int fx,
+                          const double* map12_host, const double* rot9_host, const double* ratio3_host, const void* moving, int moving_f64,
+                          int mz, int my, int mx, double* carried, void* warped, int warped_f64, void* stream);
+
 #pragma GCC visibility pop
 
 #ifdef __cplusplus
