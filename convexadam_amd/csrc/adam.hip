@@ -160,7 +160,9 @@ enum class AdamFwd { Tile, March, Lds, FastBox3, FastChain, Smoother };
 enum class AdamGrad { Exact, Fast };
 enum class AdamAdj { Tile, March, Lds, FastBox3, FastChainUpdate, SmootherFastUpdate, SmootherUpdate };
 // prediv: k_warp_grad stores gU / 27 and the adjoint tiles take their taps so -- one field, so the two launches cannot disagree
-struct AdamPlan { AdamFwd fwd; int fwd_variant; AdamGrad grad; bool prediv; AdamAdj adj; int adj_variant; };
+// wt_*: which kernels store their outputs write-through (option adam_wt: 1 forward tiles, 2 k_warp_grad, 4 adjoint + Adam tiles, 8 the fast
+// modes' kernels of adamfast.hip); the other arms never see the option
+struct AdamPlan { AdamFwd fwd; int fwd_variant; AdamGrad grad; bool prediv; AdamAdj adj; int adj_variant; bool wt_fwd, wt_grad, wt_adj; };
 
 // the k_box3_tile variant (>= 1000) that runs the exact forward (U = box(P)) or adjoint (box^T(gU) + update of P, m, v, gradient copy
 // into gsave) pass of this run, or 0 = no tiles.  The tiles issue 16-byte accesses: every pointer of the pass takes part.
@@ -183,13 +185,16 @@ static AdamPlan adam_plan(const AdamRun& r, bool packaged, const float* gU, cons
         variant = box3_tile_choice(o, r, backward, gU, gsave);
         kernel = variant ? Kernel::Tile : march ? Kernel::March : Kernel::Lds;
     };
-    AdamPlan p = {AdamFwd::Smoother, 0, r.fast ? AdamGrad::Fast : AdamGrad::Exact, false, AdamAdj::SmootherUpdate, 0};
+    AdamPlan p = {AdamFwd::Smoother, 0, r.fast ? AdamGrad::Fast : AdamGrad::Exact, false, AdamAdj::SmootherUpdate, 0, false, false, false};
     if (r.fast == 2 && packaged) p.fwd = AdamFwd::FastBox3;                    // "fast_all": separable forward boxes too
     else if (r.fast == 2 && chain) p.fwd = AdamFwd::FastChain;                 // ... for a box chain of the sweep
     else if (packaged) box3(false, p.fwd, p.fwd_variant);
     if (r.fast) p.adj = packaged ? AdamAdj::FastBox3 : chain ? AdamAdj::FastChainUpdate : AdamAdj::SmootherFastUpdate;
     else if (packaged) box3(true, p.adj, p.adj_variant);
     p.prediv = p.adj == AdamAdj::Tile && o.box_prediv != 0;
+    p.wt_fwd = p.fwd == AdamFwd::Tile ? (o.adam_wt & 1) != 0 : p.fwd == AdamFwd::FastBox3 && (o.adam_wt & 8) != 0;
+    p.wt_grad = (o.adam_wt & (p.grad == AdamGrad::Exact ? 2 : 8)) != 0;
+    p.wt_adj = p.adj == AdamAdj::Tile ? (o.adam_wt & 4) != 0 : p.adj == AdamAdj::FastBox3 && (o.adam_wt & 8) != 0;
     return p;
 }
 
@@ -245,7 +250,7 @@ extern "C" int cvx_smooth_fast_f32(const float* in, int h, int w, int d, const c
 
 extern "C" int cvx_box3_fast_f32(const float* in, int h, int w, int d, float* out, void* stream) {
     CVX_REQUIRE(in && out && in != out && h > 0 && w > 0 && d > 0, "cvx_box3_fast_f32: bad arguments");
-    return cvx::launch_box3_fast(in, out, h, w, d, nullptr, nullptr, nullptr, 1.0, 1.0, nullptr, as_stream(stream));
+    return cvx::launch_box3_fast(in, out, h, w, d, nullptr, nullptr, nullptr, 1.0, 1.0, nullptr, false, as_stream(stream));
 }
 
 // keep_state = false (whole-pair pipeline): P, m, v are scratch there and the result is U of the LAST forward pass
@@ -294,27 +299,27 @@ int cvx::adam_run_impl(const AdamRun& r) {
 
     auto forward_step = [&]() -> int {     // U = smooth(P)
         switch (plan.fwd) {
-        case AdamFwd::Tile:      return launch_box3_tile(P, U, h, w, d, plan.fwd_variant, false, nullptr, nullptr, nullptr, ac, nullptr, false, s);
+        case AdamFwd::Tile:      return launch_box3_tile(P, U, h, w, d, plan.fwd_variant, false, nullptr, nullptr, nullptr, ac, nullptr, false, plan.wt_fwd, s);
         case AdamFwd::March:     return launch_box3_march(P, U, h, w, d, false, nullptr, nullptr, nullptr, ac, nullptr, s);
         case AdamFwd::Lds:       return launch_box3x3(P, U, h, w, d, false, nullptr, nullptr, nullptr, ac, nullptr, s);
-        case AdamFwd::FastBox3:  return launch_box3_fast(P, U, h, w, d, nullptr, nullptr, nullptr, 1.0, 1.0, nullptr, s);
+        case AdamFwd::FastBox3:  return launch_box3_fast(P, U, h, w, d, nullptr, nullptr, nullptr, 1.0, 1.0, nullptr, plan.wt_fwd, s);
         case AdamFwd::FastChain: return launch_boxchain_fast(P, U, h, w, d, *sm, false, s);
         case AdamFwd::Smoother:  return launch_smoother(P, U, t1, 3, h, w, d, *sm, false, s);
         }
     };
     auto gradient_step = [&](const AdamPlan& pl) -> int {     // gU = d loss / dU
         switch (pl.grad) {
-        case AdamGrad::Exact: return launch_warp_grad(Fcl, Mcl, C, h, w, d, U, r.base_h, r.base_w, r.base_d, gsc, cH, cW, cD, gU, r.f16_features, pl.prediv, s);
-        case AdamGrad::Fast:  return launch_warp_grad_fast(Fcl, Mcl, C, h, w, d, U, r.base_h, r.base_w, r.base_d, gsc, cH, cW, cD, gU, r.f16_features, s);
+        case AdamGrad::Exact: return launch_warp_grad(Fcl, Mcl, C, h, w, d, U, r.base_h, r.base_w, r.base_d, gsc, cH, cW, cD, gU, r.f16_features, pl.prediv, pl.wt_grad, s);
+        case AdamGrad::Fast:  return launch_warp_grad_fast(Fcl, Mcl, C, h, w, d, U, r.base_h, r.base_w, r.base_d, gsc, cH, cW, cD, gU, r.f16_features, pl.wt_grad, s);
         }
     };
     auto update_step = [&](const AdamPlan& pl, float* gsave) -> int {     // G = smooth^T(gU); Adam update of P, m, v with G; gsave = G
         int rc = CVX_OK;
         switch (pl.adj) {                  // the three-box kernels update and copy in their last pass ...
-        case AdamAdj::Tile:     return launch_box3_tile(gU, nullptr, h, w, d, pl.adj_variant, true, P, m, v, ac, gsave, pl.prediv, s);
+        case AdamAdj::Tile:     return launch_box3_tile(gU, nullptr, h, w, d, pl.adj_variant, true, P, m, v, ac, gsave, pl.prediv, pl.wt_adj, s);
         case AdamAdj::March:    return launch_box3_march(gU, nullptr, h, w, d, true, P, m, v, ac, gsave, s);
         case AdamAdj::Lds:      return launch_box3x3(gU, nullptr, h, w, d, true, P, m, v, ac, gsave, s);
-        case AdamAdj::FastBox3: return launch_box3_fast(gU, nullptr, h, w, d, P, m, v, bc1, bc2, gsave, s);
+        case AdamAdj::FastBox3: return launch_box3_fast(gU, nullptr, h, w, d, P, m, v, bc1, bc2, gsave, pl.wt_adj, s);
         // ... the sweep smoothers leave G in t2: a box chain through the separable passes (adjoint = reversed box order), a Gaussian
         // through its exact 1-D convolutions; the update as an element-wise kernel
         case AdamAdj::FastChainUpdate:    rc = launch_boxchain_fast(gU, t2, h, w, d, *sm, true, s); break;

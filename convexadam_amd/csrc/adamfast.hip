@@ -37,7 +37,8 @@ __device__ __forceinline__ float4 wf_load_rec(__amdgpu_buffer_rsrc_t rsrc, unsig
     }
     return buffer_load16(rsrc, lane_off, uni_off);
 }
-template <bool HALF>
+// WT (option adam_wt, bit 8): gU leaves as write-through stores
+template <bool HALF, bool WT>
 __global__ __launch_bounds__(256) void k_warp_grad_fast(const float* __restrict__ F2, const float* __restrict__ M2, int CP,
                                                         int h, int w, int d, const float* __restrict__ U,
                                                         const float* __restrict__ bh, const float* __restrict__ bw,
@@ -147,6 +148,7 @@ __global__ __launch_bounds__(256) void k_warp_grad_fast(const float* __restrict_
     g[1] = fdiv(((float)w / 2.0f) * giy, sc1);
     g[2] = fdiv(((float)d / 2.0f) * gix, sc2);
     const float uc3[3] = {uH, uW, uD};
+    const __amdgpu_buffer_rsrc_t gr = __builtin_amdgcn_make_buffer_rsrc(gU, 0, (int)(WT ? 12u * (unsigned)V : 0u), 0x00020000);
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
         const float uc = uc3[a];
@@ -158,12 +160,13 @@ __global__ __launch_bounds__(256) void k_warp_grad_fast(const float* __restrict_
         tt = acc +  (cH * (2.0f * (uc - nb[a][3]))); acc = z > 0 ? tt : acc;
         tt = acc + -(cW * (2.0f * (nb[a][4] - uc))); acc = y < w - 1 ? tt : acc;
         tt = acc +  (cW * (2.0f * (uc - nb[a][5]))); acc = y > 0 ? tt : acc;
-        (gU + (size_t)a * V)[p] = acc;
+        if (WT) buffer_store4<true>(gr, 4u * p, (4u * (unsigned)V) * (unsigned)a, acc);
+        else (gU + (size_t)a * V)[p] = acc;
     }
 }
 
 int launch_warp_grad_fast(const float* Fcl, const float* Mcl, int C, int h, int w, int d, const float* U, const float* bh,
-                          const float* bw, const float* bd, float gsc, float cH, float cW, float cD, float* gU, bool half, hipStream_t s) {
+                          const float* bw, const float* bd, float gsc, float cH, float cW, float cD, float* gU, bool half, bool wt, hipStream_t s) {
     const int CP = (C + 3) / 4 * 4;
     // 32-bit byte offsets into the chunked feature volumes (buffer descriptors): same limit as launch_warp_grad (warp.hip)
     if ((size_t)(CP / 4) * ((size_t)h * w * d + 1) * 16 >= ((size_t)1 << 31)) return fail(CVX_ERR_UNSUPPORTED, "warp_grad_fast: control grid too large (%zu voxels x %d channels)", (size_t)h * w * d, C);
@@ -172,8 +175,11 @@ int launch_warp_grad_fast(const float* Fcl, const float* Mcl, int C, int h, int 
     const int octant = oc >= 2 && oc <= 64 ? oc : (oc == 1 && ntx >= 2 && nty >= 2 && ntz >= 2) ? 1 : 0;       // >= 2: z-groups of that many tiles
     const dim3 gv(octant == 1 ? (unsigned)(8 * ((ntx + 1) / 2) * ((nty + 1) / 2) * ((ntz + 1) / 2))
                   : octant >= 2 ? (unsigned)((ntx * nty * ((ntz + octant - 1) / octant) * octant + 7) / 8 * 8) : (unsigned)((ntx * nty * ntz + 7) / 8 * 8));     // multiple of the 8 XCDs
-    if (half) hipLaunchKernelGGL(k_warp_grad_fast<true>, gv, dim3(256), 0, s, Fcl, Mcl, CP, h, w, d, U, bh, bw, bd, 2.0f * gsc, cH, cW, cD, gU, octant);
-    else hipLaunchKernelGGL(k_warp_grad_fast<false>, gv, dim3(256), 0, s, Fcl, Mcl, CP, h, w, d, U, bh, bw, bd, 2.0f * gsc, cH, cW, cD, gU, octant);
+#define CVX_WF_LAUNCH(H, T) hipLaunchKernelGGL((k_warp_grad_fast<H, T>), gv, dim3(256), 0, s, Fcl, Mcl, CP, h, w, d, U, bh, bw, bd, 2.0f * gsc, cH, cW, cD, gU, octant)
+    if (half) { if (wt) CVX_WF_LAUNCH(true, true); else CVX_WF_LAUNCH(true, false); }
+    else if (wt) CVX_WF_LAUNCH(false, true);
+    else CVX_WF_LAUNCH(false, false);
+#undef CVX_WF_LAUNCH
     return check_last("warp_grad_fast");
 }
 
@@ -215,7 +221,9 @@ static AdamFastConsts adam_fast_consts(double bc1, double bc2) {
 // a round are requested one round ahead -- those of the first round before phase Z -- so that their latency hides behind the boxes).
 // Tile order: z fastest, and XCD q (workgroups are dealt round-robin to the 8 XCDs) takes the q-th contiguous slab of tiles: the
 // halo planes that z-neighbours share are re-read from the XCD's own L2, not from the Infinity Cache.
-template <int TZ, int TY, int TXQ, bool ADAM>
+// WT (option adam_wt, bit 8): every output of the epilogue -- out; P, m, v, gsave -- leaves as a write-through store through a descriptor
+// of its channel (the launcher passes WT only for channels below 2 GiB).
+template <int TZ, int TY, int TXQ, bool ADAM, bool WT>
 __global__ __launch_bounds__(256) void k_box3_fast(const float* __restrict__ in, float* __restrict__ out, int h, int w, int d,
                                                    float* __restrict__ P, float* __restrict__ m, float* __restrict__ v,
                                                    AdamFastConsts ac, float* __restrict__ gsave, int ntiles) {
@@ -237,6 +245,13 @@ __global__ __launch_bounds__(256) void k_box3_fast(const float* __restrict__ in,
     float* mc = ADAM ? m + (size_t)c * V : nullptr;
     float* vc = ADAM ? v + (size_t)c * V : nullptr;
     float* gs = gsave ? gsave + (size_t)c * V : nullptr;
+    const int cb = WT ? (int)(V * sizeof(float)) : 0;
+    const __amdgpu_buffer_rsrc_t ord = __builtin_amdgcn_make_buffer_rsrc(oc, 0, cb, 0x00020000), Prd = __builtin_amdgcn_make_buffer_rsrc(Pc, 0, cb, 0x00020000),
+                                 mrd = __builtin_amdgcn_make_buffer_rsrc(mc, 0, cb, 0x00020000), vrd = __builtin_amdgcn_make_buffer_rsrc(vc, 0, cb, 0x00020000),
+                                 grd = __builtin_amdgcn_make_buffer_rsrc(gs, 0, cb, 0x00020000);
+    // one store of the epilogue: 16 bytes at p[i], or the single value p[i + e]
+    auto st16 = [&](float* p, __amdgpu_buffer_rsrc_t rd, size_t i, float4 q) { if (WT) buffer_store16<true>(rd, (unsigned)i * 4u, 0, q); else *reinterpret_cast<float4*>(p + i) = q; };
+    auto st4 = [&](float* p, __amdgpu_buffer_rsrc_t rd, size_t i, float q) { if (WT) buffer_store4<true>(rd, (unsigned)i * 4u, 0, q); else p[i] = q; };
     constexpr int NQ = TXQ - 2, NI = TZ * TY * NQ, NR = (NI + NT - 1) / NT;
     // item `it` of phase X: output quad q of row r of plane j
     auto item = [&](int it, int& j, int& r, int& q, size_t& i0, bool& live, bool& full) {
@@ -302,26 +317,26 @@ __global__ __launch_bounds__(256) void k_box3_fast(const float* __restrict__ in,
         chain3<4>(a, gx - 3, d);
         float g4[4] = {a[3] * rs, a[4] * rs, a[5] * rs, a[6] * rs};
         if (!ADAM) {
-            if (full) *reinterpret_cast<float4*>(oc + i0) = make_float4(g4[0], g4[1], g4[2], g4[3]);
+            if (full) st16(oc, ord, i0, make_float4(g4[0], g4[1], g4[2], g4[3]));
             else
 #pragma unroll
-                for (int e = 0; e < 4; ++e) if (gx + e < d) oc[i0 + e] = g4[e];
+                for (int e = 0; e < 4; ++e) if (gx + e < d) st4(oc, ord, i0 + e, g4[e]);
         } else if (full) {
             float Pv[4] = {Pq.x, Pq.y, Pq.z, Pq.w}, mv[4] = {mq.x, mq.y, mq.z, mq.w}, vv[4] = {vq.x, vq.y, vq.z, vq.w};
 #pragma unroll
             for (int e = 0; e < 4; ++e) adam_update_fast(g4[e], Pv[e], mv[e], vv[e], ac);
-            *reinterpret_cast<float4*>(Pc + i0) = make_float4(Pv[0], Pv[1], Pv[2], Pv[3]);
-            *reinterpret_cast<float4*>(mc + i0) = make_float4(mv[0], mv[1], mv[2], mv[3]);
-            *reinterpret_cast<float4*>(vc + i0) = make_float4(vv[0], vv[1], vv[2], vv[3]);
-            if (gs) *reinterpret_cast<float4*>(gs + i0) = make_float4(g4[0], g4[1], g4[2], g4[3]);
+            st16(Pc, Prd, i0, make_float4(Pv[0], Pv[1], Pv[2], Pv[3]));
+            st16(mc, mrd, i0, make_float4(mv[0], mv[1], mv[2], mv[3]));
+            st16(vc, vrd, i0, make_float4(vv[0], vv[1], vv[2], vv[3]));
+            if (gs) st16(gs, grd, i0, make_float4(g4[0], g4[1], g4[2], g4[3]));
         } else {
 #pragma unroll
             for (int e = 0; e < 4; ++e)
                 if (gx + e < d) {
                     float Pv = Pc[i0 + e], mv = mc[i0 + e], vv = vc[i0 + e];
                     adam_update_fast(g4[e], Pv, mv, vv, ac);
-                    Pc[i0 + e] = Pv; mc[i0 + e] = mv; vc[i0 + e] = vv;
-                    if (gs) gs[i0 + e] = g4[e];
+                    st4(Pc, Prd, i0 + e, Pv); st4(mc, mrd, i0 + e, mv); st4(vc, vrd, i0 + e, vv);
+                    if (gs) st4(gs, grd, i0 + e, g4[e]);
                 }
         }
     }
@@ -484,12 +499,16 @@ int launch_adam_update_fast(const float* G, float* P, float* m, float* v, size_t
 
 template <int TZ, int TY, int TXQ>
 static int launch_box3_fast_t(const float* in, float* out, int h, int w, int d, float* P, float* m, float* v, AdamFastConsts ac,
-                              float* gsave, hipStream_t s) {
+                              float* gsave, bool wt, hipStream_t s) {
     constexpr int TX = 4 * TXQ - 8;
     const int ntiles = cdiv(d, TX) * cdiv(w, TY) * cdiv(h, TZ) * 3;
     const unsigned nb = (unsigned)((ntiles + 7) / 8 * 8);                        // multiple of the 8 XCDs
-    if (P) hipLaunchKernelGGL((k_box3_fast<TZ, TY, TXQ, true>), dim3(nb), dim3(256), 0, s, in, out, h, w, d, P, m, v, ac, gsave, ntiles);
-    else hipLaunchKernelGGL((k_box3_fast<TZ, TY, TXQ, false>), dim3(nb), dim3(256), 0, s, in, out, h, w, d, P, m, v, ac, gsave, ntiles);
+    wt = wt && (size_t)h * w * d * sizeof(float) < ((size_t)1 << 31);          // 32-bit byte offsets inside a channel
+#define CVX_FB_LAUNCH(A, T) hipLaunchKernelGGL((k_box3_fast<TZ, TY, TXQ, A, T>), dim3(nb), dim3(256), 0, s, in, out, h, w, d, P, m, v, ac, gsave, ntiles)
+    if (P) { if (wt) CVX_FB_LAUNCH(true, true); else CVX_FB_LAUNCH(true, false); }
+    else if (wt) CVX_FB_LAUNCH(false, true);
+    else CVX_FB_LAUNCH(false, false);
+#undef CVX_FB_LAUNCH
     return check_last("box3_fast");
 }
 
@@ -498,17 +517,17 @@ static int launch_box3_fast_t(const float* in, float* out, int h, int w, int d, 
 // 5 = 8 x 8 x 32, 6 = 4 x 10 x 24; 0 = automatic = 5 (measured on the benchmark grid 80 x 96 x 112: 5.65 ms per pair against 5.76 - 6.20
 // for the others -- the kernel moves 75 MB at ~4.3 TB/s whatever the tile, what differs is the tail of the last dispatch round).
 int launch_box3_fast(const float* in, float* out, int h, int w, int d, float* P, float* m, float* v, double bc1, double bc2,
-                     float* gsave, hipStream_t s) {
+                     float* gsave, bool wt, hipStream_t s) {
     const AdamFastConsts ac = adam_fast_consts(bc1, bc2);
     long long shape = options().fbox_tile;
     if (shape <= 0 || shape > 6) shape = 5;
     switch (shape) {
-        case 1: return launch_box3_fast_t<8, 10, 8>(in, out, h, w, d, P, m, v, ac, gsave, s);
-        case 2: return launch_box3_fast_t<8, 10, 16>(in, out, h, w, d, P, m, v, ac, gsave, s);
-        case 3: return launch_box3_fast_t<16, 10, 8>(in, out, h, w, d, P, m, v, ac, gsave, s);
-        case 4: return launch_box3_fast_t<16, 10, 16>(in, out, h, w, d, P, m, v, ac, gsave, s);
-        case 5: return launch_box3_fast_t<8, 8, 10>(in, out, h, w, d, P, m, v, ac, gsave, s);
-        default: return launch_box3_fast_t<4, 10, 8>(in, out, h, w, d, P, m, v, ac, gsave, s);
+        case 1: return launch_box3_fast_t<8, 10, 8>(in, out, h, w, d, P, m, v, ac, gsave, wt, s);
+        case 2: return launch_box3_fast_t<8, 10, 16>(in, out, h, w, d, P, m, v, ac, gsave, wt, s);
+        case 3: return launch_box3_fast_t<16, 10, 8>(in, out, h, w, d, P, m, v, ac, gsave, wt, s);
+        case 4: return launch_box3_fast_t<16, 10, 16>(in, out, h, w, d, P, m, v, ac, gsave, wt, s);
+        case 5: return launch_box3_fast_t<8, 8, 10>(in, out, h, w, d, P, m, v, ac, gsave, wt, s);
+        default: return launch_box3_fast_t<4, 10, 8>(in, out, h, w, d, P, m, v, ac, gsave, wt, s);
     }
 }
 

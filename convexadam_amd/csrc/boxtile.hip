@@ -151,7 +151,10 @@ __device__ __forceinline__ void bt_wait(const int* flags, int Y, int planes, int
 // census (option tile_census_ptr): per wavefront 8 words {start, pass 1 done, barrier 1 passed (SYNC: first pass-2 item's wait over),
 // pass 2 done, barrier 2 passed (SYNC: first pass-3 item's wait over), pass 3 done, 0, placement} in 100 MHz ticks, workgroups < 1024;
 // a wavefront without items in a pass leaves its SYNC stamp 0.
-template <int TZ, int TY, int TXQ, int NW, int WPS, bool BACKWARD, bool ADAM, bool PREDIV, bool SYNC>
+// WT (option adam_wt, bits 1 and 4): the last pass's stores of the Adam loop -- U forward; P, m, v and gsave with ADAM -- are write-through,
+// so the kernel's end has no dirty lines to write back.  Forward through a buffer descriptor; the adjoint + Adam form has no scalar
+// registers left for four more descriptors and stores through the 64-bit addresses it loads from (global_store16_wt).
+template <int TZ, int TY, int TXQ, int NW, int WPS, bool BACKWARD, bool ADAM, bool PREDIV, bool SYNC, bool WT>
 __global__ __launch_bounds__(64 * NW, WPS) void k_box3_tile(const float* __restrict__ in, float* __restrict__ out, int h, int w, int d,
                                                            int ntz, int nty, int ntx, int ntiles, int NS1, int NS2, int NS3, FastDiv dvz, FastDiv dvx, FastDiv dvy,
                                                            FastDiv dn1, FastDiv dn2, FastDiv dn3, float* __restrict__ P, float* __restrict__ m, float* __restrict__ v, AdamConsts ac,
@@ -179,6 +182,7 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_box3_tile(const float* __restr
     const float* ic = in + (size_t)c * V;
     float* oc = out ? out + (size_t)c * V : nullptr;
     const __amdgpu_buffer_rsrc_t ir = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(ic), 0, (int)(V * sizeof(float)), 0x00020000);
+    const __amdgpu_buffer_rsrc_t orr = __builtin_amdgcn_make_buffer_rsrc(oc, 0, (int)((WT && !BACKWARD) ? V * sizeof(float) : 0), 0x00020000);      // U's channel (WT forward only)
     const int tid = threadIdx.x, q = tid & 15, slot = tid >> 4;
     const int wd = w * d;
     if (SYNC) {
@@ -312,7 +316,9 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_box3_tile(const float* __restr
                 if (z0 + p0 + k >= h) return;
                 const size_t o = o0 + (size_t)k * wd;
                 if (!BACKWARD) {
-                    *reinterpret_cast<float4*>(oc + o) = make_float4(div_exact<27>(fin[0]), div_exact<27>(fin[1]), div_exact<27>(fin[2]), div_exact<27>(fin[3]));
+                    const float4 u4 = make_float4(div_exact<27>(fin[0]), div_exact<27>(fin[1]), div_exact<27>(fin[2]), div_exact<27>(fin[3]));
+                    if (WT) buffer_store16<true>(orr, (unsigned)o * 4u, 0, u4);            // (a channel is below 2 GiB: box3_tile_supported)
+                    else *reinterpret_cast<float4*>(oc + o) = u4;
                 } else if (!ADAM) {
                     *reinterpret_cast<float4*>(oc + o) = make_float4(fin[0], fin[1], fin[2], fin[3]);
                 } else {
@@ -321,10 +327,17 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_box3_tile(const float* __restr
                     float pp[4] = {p4.x, p4.y, p4.z, p4.w}, mm[4] = {m4.x, m4.y, m4.z, m4.w}, vv[4] = {v4.x, v4.y, v4.z, v4.w};
 #pragma unroll
                     for (int j = 0; j < 4; ++j) adam_update(fin[j], pp[j], mm[j], vv[j], ac);
-                    *reinterpret_cast<float4*>(Pc) = make_float4(pp[0], pp[1], pp[2], pp[3]);
-                    *reinterpret_cast<float4*>(mc) = make_float4(mm[0], mm[1], mm[2], mm[3]);
-                    *reinterpret_cast<float4*>(vc) = make_float4(vv[0], vv[1], vv[2], vv[3]);
-                    if (gsave) *reinterpret_cast<float4*>(gsave + (size_t)c * V + o) = make_float4(fin[0], fin[1], fin[2], fin[3]);
+                    if (WT) {
+                        global_store16_wt(Pc, make_float4(pp[0], pp[1], pp[2], pp[3]));
+                        global_store16_wt(mc, make_float4(mm[0], mm[1], mm[2], mm[3]));
+                        global_store16_wt(vc, make_float4(vv[0], vv[1], vv[2], vv[3]));
+                        if (gsave) global_store16_wt(gsave + (size_t)c * V + o, make_float4(fin[0], fin[1], fin[2], fin[3]));
+                    } else {
+                        *reinterpret_cast<float4*>(Pc) = make_float4(pp[0], pp[1], pp[2], pp[3]);
+                        *reinterpret_cast<float4*>(mc) = make_float4(mm[0], mm[1], mm[2], mm[3]);
+                        *reinterpret_cast<float4*>(vc) = make_float4(vv[0], vv[1], vv[2], vv[3]);
+                        if (gsave) *reinterpret_cast<float4*>(gsave + (size_t)c * V + o) = make_float4(fin[0], fin[1], fin[2], fin[3]);
+                    }
                 }
             };
             bt_walk(L, load, [](BTWin&) {}, emit);
@@ -346,7 +359,7 @@ bool box3_tile_fwd_supported(const float* in, const float* out, int h, int w, in
 
 template <int TZ, int TY, int TXQ, int NW, int WPS>
 static int launch_tile_t(const float* in, float* out, int h, int w, int d, int ns1, int ns2, int ns3, bool backward, float* P, float* m, float* v,
-                         AdamConsts ac, float* gsave, bool prediv, hipStream_t s) {
+                         AdamConsts ac, float* gsave, bool prediv, bool wt, hipStream_t s) {
     const int ntz = cdiv(h, TZ), nty = cdiv(w, TY), ntx = cdiv(d, 4 * TXQ);
     const int ntiles = 3 * ntz * nty * ntx;
     const unsigned nb = (unsigned)((ntiles + 7) / 8 * 8);
@@ -357,12 +370,15 @@ static int launch_tile_t(const float* in, float* out, int h, int w, int d, int n
     // debugging aid (option tile_census_ptr, tools/boxtile_census.py): forward tiles from word 0, adjoint tiles from word 8 * 16 * 1024
     unsigned long long* census = reinterpret_cast<unsigned long long*>(options().tile_census_ptr);
     if (census && backward) census += 8 * 16 * 1024;
-#define CVX_BT_LAUNCH(B, A, D, Y) hipLaunchKernelGGL((k_box3_tile<TZ, TY, TXQ, NW, WPS, B, A, D, Y>), dim3(nb), dim3(64 * NW), 0, s, in, out, h, w, d, ntz, nty, ntx, ntiles, a1, a2, a3, fastdiv_make(ntz), fastdiv_make(ntx), fastdiv_make(nty), fastdiv_make(a1), fastdiv_make(a2), fastdiv_make(a3), P, m, v, ac, gsave, census)
-#define CVX_BT_SYNC(B, A, D) do { if (sync) CVX_BT_LAUNCH(B, A, D, true); else CVX_BT_LAUNCH(B, A, D, false); } while (0)
-    if (!backward) CVX_BT_SYNC(false, false, false);
-    else if (!P) { if (prediv) CVX_BT_SYNC(true, false, true); else CVX_BT_SYNC(true, false, false); }
-    else if (prediv) CVX_BT_SYNC(true, true, true);
-    else CVX_BT_SYNC(true, true, false);
+#define CVX_BT_LAUNCH(B, A, D, Y, T) hipLaunchKernelGGL((k_box3_tile<TZ, TY, TXQ, NW, WPS, B, A, D, Y, T>), dim3(nb), dim3(64 * NW), 0, s, in, out, h, w, d, ntz, nty, ntx, ntiles, a1, a2, a3, fastdiv_make(ntz), fastdiv_make(ntx), fastdiv_make(nty), fastdiv_make(a1), fastdiv_make(a2), fastdiv_make(a3), P, m, v, ac, gsave, census)
+#define CVX_BT_SYNC(B, A, D, T) do { if (sync) CVX_BT_LAUNCH(B, A, D, true, T); else CVX_BT_LAUNCH(B, A, D, false, T); } while (0)
+    // (adjoint + Adam with the readiness flags AND write-through stores needs 20-28 bytes of scratch per lane: that pair keeps plain stores)
+#define CVX_BT_ADAM(D) do { if (wt && !sync) CVX_BT_LAUNCH(true, true, D, false, true); else CVX_BT_SYNC(true, true, D, false); } while (0)
+    if (!backward) { if (wt) CVX_BT_SYNC(false, false, false, true); else CVX_BT_SYNC(false, false, false, false); }
+    else if (!P) { if (prediv) CVX_BT_SYNC(true, false, true, false); else CVX_BT_SYNC(true, false, false, false); }      // (G to `out`: no pass of the loop, plain stores)
+    else if (prediv) CVX_BT_ADAM(true);
+    else CVX_BT_ADAM(false);
+#undef CVX_BT_ADAM
 #undef CVX_BT_SYNC
 #undef CVX_BT_LAUNCH
     return check_last("box3_tile");
@@ -376,19 +392,19 @@ static int launch_tile_t(const float* in, float* out, int h, int w, int d, int n
 // footprint of the stage tiles leaves no room for more (a 64-register, 8-wavefront build of kind 1 spills and takes 25 us).
 // prediv (adjoint only): the input taps are gU / 27 already (launch_warp_grad(.., prediv = true)).
 int launch_box3_tile(const float* in, float* out, int h, int w, int d, int variant, bool backward, float* P, float* m, float* v, AdamConsts ac,
-                     float* gsave, bool prediv, hipStream_t s) {
+                     float* gsave, bool prediv, bool wt, hipStream_t s) {
     const int kind = variant / 1000, ns = variant % 1000;
     int ns1 = ns / 100, ns2 = (ns / 10) % 10, ns3 = ns % 10;
     prediv = prediv && backward;
     if (kind == 1) {
         if (!ns) { ns1 = 5; ns2 = 3; ns3 = 4; }
-        return launch_tile_t<12, 8, 14, 8, 4>(in, out, h, w, d, ns1, ns2, ns3, backward, P, m, v, ac, gsave, prediv, s);
+        return launch_tile_t<12, 8, 14, 8, 4>(in, out, h, w, d, ns1, ns2, ns3, backward, P, m, v, ac, gsave, prediv, wt, s);
     }
     if (!ns) { ns1 = 4; ns2 = 3; ns3 = 4; }
-    return launch_tile_t<12, 16, 14, 16, 4>(in, out, h, w, d, ns1, ns2, ns3, backward, P, m, v, ac, gsave, prediv, s);
+    return launch_tile_t<12, 16, 14, 16, 4>(in, out, h, w, d, ns1, ns2, ns3, backward, P, m, v, ac, gsave, prediv, wt, s);
 }
 int launch_box3_tile_fwd(const float* in, float* out, int h, int w, int d, int variant, hipStream_t s) {
-    return launch_box3_tile(in, out, h, w, d, variant, false, nullptr, nullptr, nullptr, AdamConsts{}, nullptr, false, s);
+    return launch_box3_tile(in, out, h, w, d, variant, false, nullptr, nullptr, nullptr, AdamConsts{}, nullptr, false, false, s);
 }
 
 // automatic choice (option box_fwd_tile / box_bwd_tile = -1): the large tiles when they fill the chip

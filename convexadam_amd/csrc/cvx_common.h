@@ -132,7 +132,11 @@ static inline size_t ws_query(const Carver& m) { return m.used ? m.used + 256 : 
     X(box_prediv,          "CVX_BOX_PREDIV",            1)  /* exact Adam loop with the adjoint boxes on tiles: 1 (default) = k_warp_grad stores gU / 27 and the tiles do not divide their input taps,
                                                                   0 = the tiles divide every tap they load (bit-identical) */ \
     X(tile_census_ptr,     nullptr,                     0)  /* debugging aid: device address of a uint64 buffer of 2 x 8 x 16 x 1024 words; k_box3_tile records per wavefront the clocks of its passes
-                                                                  (boxtile.hip, tools/boxtile_census.py; 0 = off) */
+                                                                  (boxtile.hip, tools/boxtile_census.py; 0 = off) */ \
+    X(adam_wt,             "CVX_ADAM_WT",               1)  /* Adam loop: a kernel's outputs leave as write-through (sc1) stores, so that its end finds no dirty lines to write back from the eight
+                                                                  L2s; one bit per kernel: 1 (default) = U of the forward tiles (68.4-69.1 against 71.1-71.3 us per iteration), 2 = gU of k_warp_grad
+                                                                  (4-byte stores: inside the noise), 4 = P, m, v (+ gradient copy) of the adjoint + Adam tiles (MEASURED SLOWER, 72.8-73.1 us), 8 = the
+                                                                  fast modes' kernels of adamfast.hip (inside the noise); bit-identical; read once per run into the plan */
 #define X(name, env, dflt) long long name;
 struct Options { CVX_OPTIONS(X) };
 #undef X
@@ -221,9 +225,27 @@ __device__ __forceinline__ void lds_store4(float* p, f32x4 v) { *(volatile lds_f
 // 16-byte load through a buffer descriptor: address = descriptor base + per-lane byte offset (VGPR) + wave-uniform byte offset (SGPR);
 // no 64-bit vector address arithmetic and half the address registers of the flat form
 typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float4 buffer_load16(__amdgpu_buffer_rsrc_t rsrc, unsigned lane_off, unsigned uni_off) {
     const i32x4 v = __builtin_bit_cast(i32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)lane_off, (int)uni_off, 0));
     return make_float4(__int_as_float(v.x), __int_as_float(v.y), __int_as_float(v.z), __int_as_float(v.w));
+}
+
+// Write-through (aux 16 = sc1) stores through a buffer descriptor, addressed as buffer_load16: the bytes go to memory as they are stored
+// instead of staying dirty in the XCD's L2 until the kernel's end writes them back (option adam_wt).  WT = false: the same store, plain
+template <bool WT>
+__device__ __forceinline__ void buffer_store16(__amdgpu_buffer_rsrc_t rsrc, unsigned lane_off, unsigned uni_off, float4 v) {
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rsrc, (int)lane_off, (int)uni_off, WT ? 16 : 0);
+}
+template <bool WT>
+__device__ __forceinline__ void buffer_store4(__amdgpu_buffer_rsrc_t rsrc, unsigned lane_off, unsigned uni_off, float v) {
+    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rsrc, (int)lane_off, (int)uni_off, WT ? 16 : 0);
+}
+// the 16-byte write-through store to a 64-bit address, for a kernel that has no scalar registers left for descriptors (k_box3_tile's
+// adjoint + Adam form: P, m, v and the gradient copy would take four).  The trailing s_nop keeps the compiler's next instruction from
+// overwriting the data registers before the store has read them
+__device__ __forceinline__ void global_store16_wt(float* p, float4 v) {
+    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(p), "v"(__builtin_bit_cast(f32x4, v)) : "memory");
 }
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -518,20 +540,21 @@ int box3_tile_fwd_auto(int h, int w, int d);       // variant for this grid, 0 =
 // the same tiles for the exact adjoint boxes (ATen's avg_pool3d_backward order), optionally with the Adam update in the last pass
 bool box3_tile_supported(const float* in, const float* out, int h, int w, int d, const float* P, const float* m, const float* v, const float* gsave);
 // (prediv: the adjoint's input is gU / 27 already, launch_warp_grad(.., prediv = true))
+// (wt: the pass's outputs -- U forward, P, m, v and gsave with the Adam update -- as write-through stores, option adam_wt)
 int launch_box3_tile(const float* in, float* out, int h, int w, int d, int variant, bool backward, float* P, float* m, float* v, AdamConsts ac,
-                     float* gsave, bool prediv, hipStream_t s);
+                     float* gsave, bool prediv, bool wt, hipStream_t s);
 // warp.hip: [C][V] -> [CP/4][V][4] feature copies and the warp + data-term gradient of one Adam iteration
 // (half: records of four half-precision values -- fp16 storage of the pooled features -- instead of four floats)
 int launch_to_chunked(const float* in, int C, size_t V, float* out, bool half, hipStream_t s);
 int launch_warp_grad(const float* Fcl, const float* Mcl, int C, int h, int w, int d, const float* U, const float* bh,
-                     const float* bw, const float* bd, float gsc, float cH, float cW, float cD, float* gU, bool half, bool prediv, hipStream_t s);
+                     const float* bw, const float* bd, float gsc, float cH, float cW, float cD, float* gU, bool half, bool prediv, bool wt, hipStream_t s);
 // adamfast.hip: adam_mode "fast" -- FMA / factored warp + gradient (float32 records) and the separable adjoint boxes with the Adam
 // update in the epilogue (P != nullptr: in-place update of P, m, v with G = box(in); P == nullptr: out = box(in)); bc1, bc2 = the bias
 // corrections 1 - beta^step of this iteration
 int launch_warp_grad_fast(const float* Fcl, const float* Mcl, int C, int h, int w, int d, const float* U, const float* bh,
-                          const float* bw, const float* bd, float gsc, float cH, float cW, float cD, float* gU, bool half, hipStream_t s);
+                          const float* bw, const float* bd, float gsc, float cH, float cW, float cD, float* gU, bool half, bool wt, hipStream_t s);
 int launch_box3_fast(const float* in, float* out, int h, int w, int d, float* P, float* m, float* v, double bc1, double bc2,
-                     float* gsave, hipStream_t s);
+                     float* gsave, bool wt, hipStream_t s);
 // the same arithmetic for a chain of boxes (the sweep's kovesi splines): three 1-D passes, [3][h][w][d], in == out allowed
 bool boxchain_fast_supported(const cvx_smoother& sm, int h, int w, int d);
 int launch_boxchain_fast(const float* in, float* out, int h, int w, int d, const cvx_smoother& sm, bool reverse, hipStream_t s);

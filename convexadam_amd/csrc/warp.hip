@@ -54,7 +54,8 @@ __device__ __forceinline__ float4 buffer_load8h(__amdgpu_buffer_rsrc_t rsrc, uns
 // HALF: records of four half-precision values (k_to_chunked_h) instead of four floats; buffer loads only
 // PREDIV: gU receives the adjoint boxes' taps gU / 27 (the expression of k_box3_tile's BACKWARD prep, -0.0 kept), for the tiles that take
 // them divided (launch_box3_tile(.., prediv = true)): one division per value instead of one per load there
-template <bool BUF, bool HALF = false, bool PREDIV = false>
+// WT (option adam_wt, bit 2): the three components of gU leave as write-through stores
+template <bool BUF, bool HALF = false, bool PREDIV = false, bool WT = false>
 __global__ __launch_bounds__(256) void k_warp_grad(const float* __restrict__ F2, const float* __restrict__ M2, int C, int CP,
                                                    int h, int w, int d, const float* __restrict__ U,
                                                    const float* __restrict__ bh, const float* __restrict__ bw,
@@ -161,6 +162,7 @@ __global__ __launch_bounds__(256) void k_warp_grad(const float* __restrict__ F2,
 #pragma unroll
         for (int k = 0; k < 6; ++k) nb[a][k] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ur, (int)nboff[k], (int)(4u * (unsigned)V) * a, 0));
     const float uc3[3] = {uH, uW, uD};
+    const __amdgpu_buffer_rsrc_t gr = __builtin_amdgcn_make_buffer_rsrc(gU, 0, (int)(WT ? 12u * (unsigned)V : 0u), 0x00020000);
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
         const float uc = uc3[a];
@@ -171,7 +173,9 @@ __global__ __launch_bounds__(256) void k_warp_grad(const float* __restrict__ F2,
         t = acc +  (cH * (2.0f * (uc - nb[a][3]))); acc = z > 0 ? t : acc;
         t = acc + -(cW * (2.0f * (nb[a][4] - uc))); acc = y < w - 1 ? t : acc;
         t = acc +  (cW * (2.0f * (uc - nb[a][5]))); acc = y > 0 ? t : acc;
-        (gU + (size_t)a * V)[p] = PREDIV ? (acc == 0.0f ? acc : div_exact<27>(acc)) : acc;
+        const float ga = PREDIV ? (acc == 0.0f ? acc : div_exact<27>(acc)) : acc;
+        if (WT) buffer_store4<true>(gr, 4u * p, (4u * (unsigned)V) * (unsigned)a, ga);
+        else (gU + (size_t)a * V)[p] = ga;
     }
     if (census && threadIdx.x == 0) census[4 * blockIdx.x + 2] = __builtin_amdgcn_s_memrealtime();
 }
@@ -186,7 +190,7 @@ int launch_to_chunked(const float* in, int C, size_t V, float* out, bool half, h
 }
 
 int launch_warp_grad(const float* Fcl, const float* Mcl, int C, int h, int w, int d, const float* U, const float* bh,
-                     const float* bw, const float* bd, float gsc, float cH, float cW, float cD, float* gU, bool half, bool prediv, hipStream_t s) {
+                     const float* bw, const float* bd, float gsc, float cH, float cW, float cD, float* gU, bool half, bool prediv, bool wt, hipStream_t s) {
     const int CP = (C + 3) / 4 * 4;
     const dim3 gv((unsigned)((cdiv(d, 16) * cdiv(w, 4) * cdiv(h, 4) + 7) / 8 * 8));     // multiple of the 8 XCDs
     unsigned long long* census = reinterpret_cast<unsigned long long*>(options().census_ptr);       // debugging aid: slots [8192, ..)
@@ -194,10 +198,12 @@ int launch_warp_grad(const float* Fcl, const float* Mcl, int C, int h, int w, in
     const FastDiv dx = fastdiv_make(cdiv(d, 16)), dy = fastdiv_make(cdiv(w, 4));
     const float sc0 = (float)((h - 1) / 2.0), sc1 = (float)((w - 1) / 2.0), sc2 = (float)((d - 1) / 2.0);
 #define CVX_WG_LAUNCH(...) hipLaunchKernelGGL((k_warp_grad<__VA_ARGS__>), gv, dim3(256), 0, s, Fcl, Mcl, C, CP, h, w, d, U, bh, bw, bd, gsc, cH, cW, cD, gU, census, dx, dy, sc0, sc1, sc2)
-    if (half) { if (prediv) CVX_WG_LAUNCH(true, true, true); else CVX_WG_LAUNCH(true, true); }
-    else if (options().warp_flat) { if (prediv) CVX_WG_LAUNCH(false, false, true); else CVX_WG_LAUNCH(false); }
-    else if (prediv) CVX_WG_LAUNCH(true, false, true);
-    else CVX_WG_LAUNCH(true);
+#define CVX_WG_WT(B, H, D) do { if (wt) CVX_WG_LAUNCH(B, H, D, true); else CVX_WG_LAUNCH(B, H, D, false); } while (0)
+    if (half) { if (prediv) CVX_WG_WT(true, true, true); else CVX_WG_WT(true, true, false); }
+    else if (options().warp_flat) { if (prediv) CVX_WG_WT(false, false, true); else CVX_WG_WT(false, false, false); }
+    else if (prediv) CVX_WG_WT(true, false, true);
+    else CVX_WG_WT(true, false, false);
+#undef CVX_WG_WT
 #undef CVX_WG_LAUNCH
     return check_last("warp_grad");
 }

@@ -82,6 +82,9 @@ int cvx_device_count(void);            /* number of visible HIP devices (0 on a 
  *   box_tile_sync       three-box tiles of the Adam loop: 1 = the passes hand over through per-row readiness flags (measured slower), 0 (default) = workgroup barriers
  *   box_prediv          exact Adam loop: 1 (default) = the warp kernel stores gU / 27 for the adjoint box tiles, 0 = the tiles divide their taps
  *   tile_census_ptr     debugging aid: device buffer of 2 x 8 x 16 x 1024 uint64 for per-wavefront pass clocks of the box tiles (0 = off)
+ *   adam_wt             Adam loop: write-through stores for the kernels' outputs, one bit per kernel (CVX_ADAM_WT; default 1): 1 = U of the forward
+ *                       box tiles, 2 = gU of the exact warp kernel, 4 = P, m, v and the gradient copy of the adjoint + Adam box tiles (not with
+ *                       box_tile_sync = 1), 8 = the kernels of the fast modes; 0 = plain stores everywhere; read once per run, bit-identical
  * Workspace sizes (cvx_*_workspace_bytes) depend on some switches: query them with the same context / options the call will use.
  *
  * State model.  Switches and the two reference-build tables below live in a CONTEXT.  Every entry point uses the context bound to the
