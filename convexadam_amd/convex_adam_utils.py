@@ -490,5 +490,5 @@ from .rigid import affine_warp, find_rigid_3d, least_trimmed_rigid, rigid_from_f
 # the script's coarse foreground mask and landmark score (l2r_2020_convexAdam_CuRIOUS.py:312-319,328-330): csrc/rigidreg.hip
 from .rigid import convex_adam_rigid, convex_stage, label_centroids, landmark_tre, rigid_samples, threshold_pool_mask  # noqa: E402,F401
 # physical-space resampling and field carry-over on the device (convex_adam_utils.py:282-351, apply_convex.py:27-78): csrc/geometry.hip
-from .geometry import (Grid, grid_of, index_map, register_images, resample_device,  # noqa: E402,F401
+from .geometry import (Grid, field_mean_device, grid_of, index_map, register_images, resample_device,  # noqa: E402,F401
                        rescale_displacement_field_device)

@@ -6,6 +6,8 @@ with SimpleITK's resampler before and after a registration (convex_adam_utils.py
     resample_device(src, src_grid, out_grid)       ITK-convention linear resampling of a (z, y, x) device tensor onto another grid
     rescale_displacement_field_device(...)         a field on the resampled fixed grid -> the original moving image's grid, axes and voxel
                                                    size and, in the same launch, that image warped by it
+    field_mean_device(field, ...)                  sums and count of a field over all voxels, a mask, or a segmentation on its own grid
+                                                   (csrc/fieldmean.hip): convex_adam_translation's reduction
     register_images(fixed_image, moving_image)     the reference tests' whole flow, one upload per image
 
 Geometry travels as `Grid` tuples (x, y, z order like SimpleITK), voxels as device tensors in (z, y, x) order like sitk.GetArrayFromImage.
@@ -18,7 +20,7 @@ from collections import namedtuple
 import numpy as np
 import torch
 
-from ._lib import check, lib, ptr, require_device_tensor, stream_ptr
+from ._lib import check, lib, ptr, require_device_tensor, stream_ptr, workspace
 
 Grid = namedtuple("Grid", "size spacing origin direction")          # x, y, z; direction: 9 values, row-major
 Registration = namedtuple("Registration", "field carried_field warped ssim_before ssim_after")
@@ -82,6 +84,15 @@ def resample_device(src, src_grid, out_grid, default=0.0):
     return torch.round(out).to(src.dtype)                       # torch.round: half to even
 
 
+def _field_layout(f, shape):
+    """(component stride, voxel stride) in elements of a contiguous (H, W, D, 3) or (3, H, W, D) field on a grid of (z, y, x) = shape"""
+    if f.dim() == 4 and tuple(f.shape) == tuple(shape) + (3,):
+        return 1, 3
+    if f.dim() == 4 and tuple(f.shape) == (3,) + tuple(shape):
+        return shape[0] * shape[1] * shape[2], 1
+    raise ValueError("field must be (H, W, D, 3) or (3, H, W, D) on the grid (z, y, x) = %s, got %s" % (tuple(shape), tuple(f.shape)))
+
+
 def field_frame(moving_grid, fixed_grid, fixed_resampled_grid):
     """R = inv(D_fixed) @ D_moving and ratio = spacing(resampled fixed) / spacing(moving), x, y, z order (convex_adam_utils.py:340-351)."""
     frame_fixed = np.array(grid_of(fixed_grid).direction).reshape(3, 3)
@@ -103,17 +114,11 @@ def rescale_displacement_field_device(field, moving_grid, fixed_grid, fixed_resa
     require_device_tensor(field, "field")
     mg, fg, rg = grid_of(moving_grid), grid_of(fixed_grid), grid_of(fixed_resampled_grid)
     shape = tuple(rg.size)[::-1]
-    V = shape[0] * shape[1] * shape[2]
     f = field.detach()
     if f.dtype not in (torch.float32, torch.float64):
         f = f.to(torch.float64)
     f = f.contiguous()
-    if f.dim() == 4 and tuple(f.shape) == shape + (3,):
-        cs, vs = 1, 3
-    elif f.dim() == 4 and tuple(f.shape) == (3,) + shape:
-        cs, vs = V, 1
-    else:
-        raise ValueError("field must be (H, W, D, 3) or (3, H, W, D) on the resampled fixed grid (z, y, x) = %s, got %s" % (shape, tuple(f.shape)))
+    cs, vs = _field_layout(f, shape)
     dev = f.device
     mx, my, mz = mg.size
     m, m64 = (None, 0)
@@ -137,6 +142,85 @@ def rescale_displacement_field_device(field, moving_grid, fixed_grid, fixed_resa
     if moving is None:
         return carried
     return (carried, warped) if want_field else warped
+
+
+_QUANTIZE = {None: 0, 0: 0, 1: 1, torch.float32: 0, torch.float16: 1}          # the `quantize` of cvx_pack_field_f64
+SEG_KIND_F64, SEG_KIND_F32, SEG_KIND_INT = 0, 1, 2
+
+
+def field_mean_device(field, field_grid=None, mask=None, seg=None, seg_grid=None, quantize=None):
+    """Sums and count of a displacement field over the voxels that count (cvx_field_mean_f64): the reduction of convex_adam_translation
+    (convex_adam_translation.py:88-103) without the field leaving the device.
+
+    field: (H, W, D, 3) or (3, H, W, D) device tensor, float32 or float64, read in place; components z, y, x.
+    quantize: None / torch.float32 / 0 = the values as they are; torch.float16 / 1 = each value through convex_adam_pt's default `dtype` round trip
+    first (float32 fields only).
+    Which voxels count: all of them; or those where `mask` ((H, W, D) device tensor) is nonzero; or those where `seg`, a (z, y, x) device
+    tensor on `seg_grid`, resampled onto `field_grid` is > 0 -- bit for bit the mask `resample_device(seg, seg_grid, field_grid) > 0`, decided
+    per voxel inside the kernel; the resampled volume is never written.  `mask` and `seg` exclude each other.
+    Returns (sums float64[3], count int64 scalar), two views of one 32-byte device buffer; nothing here waits for the device.  The mean
+    is sums / count; the order of the additions is fixed, so two calls give the same bits."""
+    out = field_mean_buffer(field, field_grid, mask, seg, seg_grid, quantize)
+    return out[:3], out[3:].view(torch.int64)[0]
+
+
+def field_mean_buffer(field, field_grid=None, mask=None, seg=None, seg_grid=None, quantize=None):
+    """field_mean_device's result as the one device buffer the kernel wrote: float64[4], the three sums and the bits of the int64 count
+    (for a caller that downloads all 32 bytes at once)."""
+    require_device_tensor(field, "field")
+    f = field.detach()
+    if f.dim() != 4:
+        raise ValueError("field must be (H, W, D, 3) or (3, H, W, D), got %s" % (tuple(f.shape),))
+    if field_grid is not None:
+        shape = tuple(grid_of(field_grid).size)[::-1]
+    elif mask is not None:
+        shape = tuple(mask.shape)
+    elif f.shape[0] == 3 and f.shape[3] != 3:
+        shape = tuple(f.shape[1:])
+    elif f.shape[3] == 3 and f.shape[0] != 3:
+        shape = tuple(f.shape[:3])
+    else:
+        raise ValueError("a field of shape %s does not say which of its layouts it is: pass field_grid" % (tuple(f.shape),))
+    if quantize not in _QUANTIZE:
+        raise ValueError("quantize must be None / torch.float32 / 0, or torch.float16 / 1")
+    if f.dtype not in (torch.float32, torch.float64):
+        f = f.to(torch.float64)
+    f = f.contiguous()
+    cs, vs = _field_layout(f, shape)
+    dev = f.device
+    if mask is not None and seg is not None:
+        raise ValueError("mask and seg exclude each other")
+    m = s = None
+    kind, sext, m12 = 0, (0, 0, 0), None
+    if mask is not None:
+        require_device_tensor(mask, "mask")
+        if mask.device != dev or tuple(mask.shape) != shape:
+            raise ValueError("mask %s on %s does not match the field's grid %s on %s" % (tuple(mask.shape), mask.device, shape, dev))
+        m = (mask.detach() != 0).to(torch.uint8).contiguous()
+    if seg is not None:
+        require_device_tensor(seg, "seg")
+        if seg_grid is None or field_grid is None:
+            raise ValueError("seg needs seg_grid and field_grid")
+        if seg.device != dev:
+            raise ValueError("field on %s, seg on %s" % (dev, seg.device))
+        sg = grid_of(seg_grid)
+        kind = SEG_KIND_F64 if seg.dtype == torch.float64 else SEG_KIND_F32 if seg.dtype == torch.float32 else SEG_KIND_INT
+        if seg.dtype.is_floating_point and kind == SEG_KIND_INT:
+            raise ValueError("seg must be float32, float64 or an integer type, got %s" % seg.dtype)
+        s, _ = _volume(seg, sg, "seg")
+        sext = tuple(sg.size)[::-1]
+        m12 = _doubles(*index_map(sg, grid_of(field_grid)))
+    out = torch.empty(4, dtype=torch.float64, device=dev)
+    L = lib()
+    with torch.cuda.device(dev):
+        nbytes = L.cvx_field_mean_workspace_bytes(*shape)
+        if nbytes == 0:
+            check(-1)
+        buf = workspace(nbytes, dev)
+        check(L.cvx_field_mean_f64(ptr(f), int(f.dtype == torch.float64), cs, vs, shape[0], shape[1], shape[2], _QUANTIZE[quantize], ptr(m), ptr(s),
+                                   kind, sext[0], sext[1], sext[2], m12, C.c_void_p(out.data_ptr()), C.c_void_p(out.data_ptr() + 24), ptr(buf),
+                                   buf.numel(), stream_ptr(dev)))
+    return out
 
 
 def resampled_grid(grid, spacing):

@@ -669,6 +669,34 @@ int cvx_field_to_grid_f64(const void* field, int field_f64, int64_t comp_stride,
                           const double* map12_host, const double* rot9_host, const double* ratio3_host, const void* moving, int moving_f64,
                           int mz, int my, int mx, double* carried, void* warped, int warped_f64, void* stream);
 
+/* Masked mean of a displacement field (csrc/fieldmean.hip) ----------------------------------------------------------------------------
+ * replaces the reduction of convex_adam_translation (src/convexAdam/convex_adam_translation.py:88-103: np.mean(field[mask], axis=0) over
+ * the resampled segmentation > 0): three float64 sums and a count, so that the field never leaves the device.
+ *   field    component c (0, 1, 2 = along z, y, x) of voxel q = (z W + y) D + x at field[c * comp_stride + q * voxel_stride] (elements), float
+ *            (field_is_f64 = 0) or double (1), read in place; the strides as in cvx_field_to_grid_f64.
+ *   quantize as in cvx_pack_field_f64: 0 = the value as it is, 1 = rounded to float16 (nearest even) and widened, what convex_adam_pt's
+ *            default dtype does to every value before the reference averages it; 1 needs a float32 field.
+ *   Which voxels count (mask and seg together are refused):
+ *     neither  every voxel
+ *     mask     [H][W][D] bytes (device), nonzero = counts
+ *     seg      [sH][sW][sD] (device) on a grid of its own, sampled per field voxel exactly as cvx_resample_linear_f64 samples a source
+ *              (map12, HOST: field index -> segmentation index; ITK's inside rule, default 0, the float64 tap sum), then converted as the
+ *              resampled volume of that source would be, then `> 0`: seg_kind 0 = float64 source, value > 0; 1 = float32 source,
+ *              (float)value > 0; 2 = integer source uploaded as float64, rint(value) > 0 (half to even).  No resampled volume is written.
+ *   sums3 (3 doubles: z, y, x) and count (DEVICE) receive the sums over the counted voxels and their number; the caller divides.  A NaN or
+ *   an infinity in a counted voxel propagates; in an excluded voxel it is never added.
+ *   The order of the additions is fixed (no floating-point atomics): block b owns voxels [b S, (b + 1) S), S = 256 * 16; thread t adds
+ *   voxels b S + k 256 + t, k = 0 .. 15, in that order from 0.0; the block's 256 accumulators are combined by acc[t] += acc[t + s], t < s,
+ *   for s = 128, 64, .., 1; a second one-block launch lets thread t add block partials t, t + 256, .. in order and runs the same tree.  The
+ *   workspace holds the block partials.
+ * CVX_ERR_INVALID_ARG before anything is launched: NULL field or outputs, an extent below 1, more than 2^31 - 1 voxels on either grid,
+ * strides that fold the components onto each other, a non-finite map12, seg without map12, mask with seg, quantize = 1 with a float64 field,
+ * outputs overlapping an input or each other; CVX_ERR_WORKSPACE: a workspace below the query's size. */
+size_t cvx_field_mean_workspace_bytes(int H, int W, int D);
+int cvx_field_mean_f64(const void* field, int field_is_f64, long long comp_stride, long long voxel_stride, int H, int W, int D, int quantize,
+                       const unsigned char* mask, const void* seg, int seg_kind, int sH, int sW, int sD, const double* map12, double* sums3,
+                       long long* count, void* workspace, size_t workspace_bytes, void* stream);
+
 #pragma GCC visibility pop
 
 #ifdef __cplusplus
