@@ -206,7 +206,12 @@ __device__ __forceinline__ CandBox cand_box(const float* __restrict__ mesh, floa
         c.b_lo = max((int)ceilf(c.ub - R + hwf), 0); c.b_hi = min((int)floorf(c.ub + R + hwf), n - 1);
         c.a_lo = max((int)ceilf(c.ua - R + hwf), 0); c.a_hi = min((int)floorf(c.ua + R + hwf), n - 1);
         c.vol = (long long)max(c.c_hi - c.c_lo + 1, 0) * max(c.b_hi - c.b_lo + 1, 0) * max(c.a_hi - c.a_lo + 1, 0);
-        c.degenerate = !(coef > 0.0f) || !(R == R) || c.vol <= 0;       // no usable bound: scan the whole window
+        // no usable bound: scan the whole window.  A bound that is not finite is none, and it always shows in qmax (coef > 0), so
+        // qmax alone is tested: a column of +Inf costs (half storage of costs above 65504) has bound = sm = +Inf and
+        // qmax = Inf - Inf = NaN, which fmaxf would turn into R = 1e-4 -- the single lattice point under u, where torch.argmin returns
+        // index 0 for a column of equal costs; a +Inf previous winner over a finite minimum (a caller's argmin, first pass) gives
+        // qmax = +Inf and scans the window as well, without the refinement below
+        c.degenerate = !(coef > 0.0f) || !(fabsf(qmax) < __builtin_inff()) || c.vol <= 0;
     };
     close_box();
     if (!c.degenerate && c.vol > refine_above && uc == uc && ub == ub && ua == ua) {

@@ -7,16 +7,24 @@ paths (tests/test_gpu_operators.py grades those kernels against the oracle bit f
                  and the Kovesi box chains as chains of avg_pool3d; the adjoint is torch autograd through the same composition;
   * grid_sample = 5-D F.grid_sample(bilinear, zeros, align_corners=False), including non-finite, huge and lattice-centre coordinates
                  and non-finite volume values.
+  * coupled_convex on cost volumes with +Inf entries and the float32 -> half rounding table: the oracle side of
+                 tests/test_gpu_fp16_edges.py (inputs in tests/fp16_edge_cases.py).
 Everything is bit-exact (np.array_equal with equal_nan and the same NaN positions).  CPU only.
 
 Which ATen convolution kernel runs depends on the thread count and the input size: with one thread a multi-channel adjoint, and at
 any thread count a volume of a single voxel, take kernels that round differently.  The oracle restates the kernel every other case
 takes, so these tests run torch with at least two threads and anchor the Gaussian on volumes of more than one voxel (the GPU tests
 still grade the single voxel against the oracle)."""
+import os
+import sys
+
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import fp16_edge_cases as E  # noqa: E402
 
 
 @pytest.fixture(autouse=True)
@@ -205,3 +213,81 @@ def test_grid_sample_lattice_centres_with_non_finite_neighbours(orc):
     assert np.isnan(got[0, 0, 1, 3]) and np.isnan(got[0, 1, 1, 4]) and np.isnan(got[1, 1, 4, 8])       # 0-weight taps: 0 * inf, 0 * NaN
     assert np.isfinite(got[0, 1, 2, 5]) and np.isfinite(got[0, 1, 3, 4])                               # beyond the upper corner: untouched
     assert np.array_equal(got[:, 3, :, :], vol[:, 3, :, :])                                            # no non-finite value nearby: exact copy
+
+
+# ---- half precision and +Inf costs: the references of tests/test_gpu_fp16_edges.py -------------------------------------------------
+def test_half_table_numpy_vs_torch():
+    """numpy's float32 -> float16 cast (the expected value of the GPU rounding tests) equals torch's at every boundary: all finite
+    halves, the midpoints to their successors (ties to even, 65520 -> Inf, 2^-25 -> 0) and the float32 neighbours of the midpoints."""
+    t = E.half_boundary_table()
+    assert t.dtype == np.float32 and t.size >= 4 * 63488 + 7
+    want = torch.from_numpy(t).half().numpy()
+    got = E.to_half(t)
+    nan = np.isnan(t)
+    assert nan.sum() == 1 and np.array_equal(np.isnan(got), nan) and np.array_equal(np.isnan(want), nan)
+    assert np.array_equal(got[~nan].view(np.uint16), want[~nan].view(np.uint16))
+    assert E.same(got.astype(np.float32), torch.from_numpy(t).half().float().numpy())
+    # the table reaches what it is there for: both results of a tie, the overflow boundary, the subnormal range, signed zeros
+    h = got.astype(np.float32)
+    assert np.isposinf(h[t == np.float32(65520.0)]).all() and (h[t == np.float32(65519.996)] == 65504).all()
+    assert (h[t == np.float32(2.0 ** -25)] == 0).all() and (h[t == np.nextafter(np.float32(2.0 ** -25), np.float32(1))] == np.float32(2.0 ** -24)).all()
+    assert np.signbit(h[(t == 0) & np.signbit(t)]).all() and not np.signbit(h[(t == 0) & ~np.signbit(t)]).any()
+    finite = np.isfinite(t)
+    assert (np.isinf(h) & finite).sum() > 4 and ((h == 0) & (t != 0)).sum() > 2
+
+
+@pytest.mark.parametrize("C,shape,hw", E.GEOMETRIES, ids=lambda v: "x".join(map(str, v)) if isinstance(v, tuple) else str(v))
+@pytest.mark.parametrize("kind", E.KINDS)
+def test_half_volume_generators_reach_their_case(orc, C, shape, hw, kind):
+    """The feature pairs of the GPU tests give, on the oracle's volume rounded to half: subnormals only / mass ties / +Inf entries
+    on both sides of 65504 / all-Inf columns beside finite ones -- from a finite float32 volume."""
+    f, m = E.feature_pair(C, shape, hw, kind)
+    assert np.isfinite(f).all() and np.isfinite(m).all() and max(np.abs(f).max(), np.abs(m).max()) < 65504
+    ref, _ = orc.correlate(f, m, hw)
+    p = E.volume_property(kind, ref)
+    assert E.property_holds(kind, ref.shape[0], p), p
+
+
+def _inf_inputs():
+    out = []
+    for hw in (2, 3):
+        for kind in E.INF_KINDS:
+            for foreign in (False, True):
+                out.append(pytest.param(kind, hw, foreign, id="%s-hw%d-%s" % (kind, hw, "foreign" if foreign else "true")))
+    return out
+
+
+@pytest.mark.parametrize("kind,hw,foreign", _inf_inputs())
+def test_coupled_convex_with_infinite_costs_vs_torch(orc, kind, hw, foreign):
+    """+Inf costs follow torch.argmin (an all-Inf column, penalised or not, gives index 0): the oracle against the operator written in
+    plain torch, with the true argmin and with one foreign displacement for every voxel."""
+    ssd = E.inf_volume(kind, hw)
+    assert np.isposinf(ssd).any() and not np.isnan(ssd).any() and np.isfinite(ssd).any()
+    if kind != "scattered":
+        assert np.isposinf(ssd).reshape(ssd.shape[0], -1).all(0).any()
+    am = E.foreign_constant_argmin(hw) if foreign else E.first_minimum(ssd)
+    mesh = orc.disp_mesh(hw)
+    assert E.same(orc.coupled_convex(ssd, am, mesh, hw), E.coupled_convex_torch(ssd, am, mesh))
+
+
+def test_coupled_convex_lattice_sheet_vs_torch(orc):
+    """An all-Inf sheet between uniform winners at (1, 1, 1): the first smoothing step puts the sheet's interior exactly on the lattice
+    point (0, 0, 0), and every pass still returns index 0 = (-2, -2, -2) there, as torch.argmin does for a column of equal costs."""
+    ssd, am, hw, x0 = E.lattice_sheet_volume()
+    mesh = orc.disp_mesh(hw)
+    assert np.array_equal(mesh[:, 93], [1, 1, 1]) and np.array_equal(mesh[:, 0], [-2, -2, -2]) and np.array_equal(mesh[:, 62], [0, 0, 0])
+    assert (am[:, :, x0] == 0).all() and (np.delete(am, x0, 2) == 93).all()
+    u0 = orc.box_zero(mesh[:, am.reshape(-1)].reshape((3,) + am.shape), 3)
+    assert E.same(u0[:, 1:-1, 1:-1, x0], np.zeros((3,) + tuple(s - 2 for s in am.shape[:2]), np.float32))
+    assert E.same(orc.coupled_convex(ssd, am, mesh, hw), E.coupled_convex_torch(ssd, am, mesh))
+
+
+@pytest.mark.parametrize("kind", ["overflow", "block"])
+def test_coupled_convex_on_overflowing_half_volume_vs_torch(orc, kind):
+    C, shape, hw = E.GEOMETRIES[0]
+    f, m = E.feature_pair(C, shape, hw, kind)
+    vol = E.widen(orc.correlate(f, m, hw)[0])
+    assert np.isposinf(vol).any()
+    mesh = orc.disp_mesh(hw)
+    for am in (E.first_minimum(vol), E.foreign_constant_argmin(hw, shape)):
+        assert E.same(orc.coupled_convex(vol, am, mesh, hw), E.coupled_convex_torch(vol, am, mesh))
