@@ -112,6 +112,9 @@ SIGNATURES = {
     "cvx_adam_run_fast_f32": (_i, _ADAM_HEAD + [_vp, _sz, _vp]),
     "cvx_adam_run_fast_all_f32": (_i, _ADAM_HEAD + [_vp, _sz, _vp]),
     "cvx_adam_run_mode_f32": (_i, _ADAM_HEAD + [C.POINTER(Smoother), _i, _vp, _sz, _vp]),
+    "cvx_const_div_make": (_i, [_f, _i, C.POINTER(C.c_float), C.POINTER(C.c_int)]),
+    "cvx_const_div_enumerate": (_i, [_f, _f]),
+    "cvx_const_div_mismatches": (C.c_longlong, [_f, _i, _i, _i, C.POINTER(C.c_uint)]),
     "cvx_smooth_fast_f32": (_i, [_vp, _i, _i, _i, C.POINTER(Smoother), _i, _vp, _vp]),
     "cvx_box3_fast_f32": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "cvx_register_pair_workspace_bytes": (_sz, [C.POINTER(PairParams)]),

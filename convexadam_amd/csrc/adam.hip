@@ -17,6 +17,8 @@
 // working set (F2, M2 = 2 x 41 MB) stays resident in the 256 MiB Infinity Cache across iterations.
 #include <math.h>
 
+#include <vector>
+
 #include "cvx_common.h"
 
 namespace cvx {
@@ -233,8 +235,8 @@ extern "C" int cvx_adam_run_fast_f32(ADAM_ABI_HEAD, ADAM_ABI_TAIL) { return cvx:
 extern "C" int cvx_adam_run_fast_all_f32(ADAM_ABI_HEAD, ADAM_ABI_TAIL) { return cvx::adam_run_impl({ADAM_ABI_ARGS, .fast = 2}); }
 
 extern "C" int cvx_adam_run_mode_f32(ADAM_ABI_HEAD, const cvx_smoother* sm, int mode, ADAM_ABI_TAIL) {
-    CVX_REQUIRE((mode & ~16) >= 0 && (mode & ~16) <= 2, "cvx_adam_run_mode_f32: mode must be 0 (exact), 1 (fast) or 2 (fast_all), + 16 for half-precision feature records");
-    return cvx::adam_run_impl({ADAM_ABI_ARGS, .sm = sm, .f16_features = (mode & 16) != 0, .fast = mode & 3});
+    CVX_REQUIRE((mode & ~48) >= 0 && (mode & ~48) <= 2, "cvx_adam_run_mode_f32: mode must be 0 (exact), 1 (fast) or 2 (fast_all), + 16 for half-precision feature records, + 32 (tests only) for IEEE divisions throughout");
+    return cvx::adam_run_impl({ADAM_ABI_ARGS, .sm = sm, .f16_features = (mode & 16) != 0, .fast = mode & 3, .ieee_div = (mode & 32) != 0});
 }
 
 extern "C" int cvx_adam_run_ex_f32(ADAM_ABI_HEAD, const cvx_smoother* sm, int feature_storage, ADAM_ABI_TAIL) {
@@ -296,6 +298,17 @@ int cvx::adam_run_impl(const AdamRun& r) {
     const AdamPlan plan = adam_plan(r, packaged, gU, nullptr), plan_save = r.grad_out ? adam_plan(r, packaged, gU, r.grad_out) : plan;
     const unsigned* const sqrt_tbl = adam_sqrt_table();
     AdamConsts ac; double bc1, bc2;        // Adam constants and bias corrections 1 - beta^step of the current iteration
+    const double beta1 = 0.9, beta2 = 0.999;
+    auto bias2 = [&](int it) { return 1.0 - pow(beta2, (double)(r.step0 + it + 1)); };
+    // the exact update divides by (float)sqrt(bias2), one value per iteration: div_const takes those the process has proven.  A run proves
+    // its own before it enqueues anything, at most 128 new ones on up to 8 threads (host cost: constdiv.hip, const_div_prove); what a
+    // longer first run leaves unproven keeps the IEEE division until a later call proves it
+    const bool constdiv = !r.fast && !r.ieee_div;
+    if (constdiv && r.niter > 0) {
+        std::vector<float> ds((size_t)r.niter);
+        for (int it = 0; it < r.niter; ++it) ds[(size_t)it] = (float)sqrt(bias2(it));
+        const_div_prove(ds.data(), r.niter, 128);
+    }
 
     auto forward_step = [&]() -> int {     // U = smooth(P)
         switch (plan.fwd) {
@@ -309,7 +322,7 @@ int cvx::adam_run_impl(const AdamRun& r) {
     };
     auto gradient_step = [&](const AdamPlan& pl) -> int {     // gU = d loss / dU
         switch (pl.grad) {
-        case AdamGrad::Exact: return launch_warp_grad(Fcl, Mcl, C, h, w, d, U, r.base_h, r.base_w, r.base_d, gsc, cH, cW, cD, gU, r.f16_features, pl.prediv, pl.wt_grad, s);
+        case AdamGrad::Exact: return launch_warp_grad(Fcl, Mcl, C, h, w, d, U, r.base_h, r.base_w, r.base_d, gsc, cH, cW, cD, gU, r.f16_features, pl.prediv, pl.wt_grad, !r.ieee_div, s);
         case AdamGrad::Fast:  return launch_warp_grad_fast(Fcl, Mcl, C, h, w, d, U, r.base_h, r.base_w, r.base_d, gsc, cH, cW, cD, gU, r.f16_features, pl.wt_grad, s);
         }
     };
@@ -337,9 +350,9 @@ int cvx::adam_run_impl(const AdamRun& r) {
     for (int it = 0; it < r.niter; ++it) {
         int rc;
         const int step = r.step0 + it + 1;
-        const double beta1 = 0.9, beta2 = 0.999;
-        bc1 = 1.0 - pow(beta1, (double)step); bc2 = 1.0 - pow(beta2, (double)step);
-        ac = {(float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)sqrt(bc2), (float)(-(1.0 / bc1)), sqrt_tbl};
+        bc1 = 1.0 - pow(beta1, (double)step); bc2 = bias2(it);
+        const float bc2s = (float)sqrt(bc2);
+        ac = {(float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), constdiv ? const_div_if_proven(bc2s) : const_div_ieee(bc2s), (float)(-(1.0 / bc1)), sqrt_tbl};
         const bool last = it == r.niter - 1;
         const bool skip = last && !r.keep_state && !r.grad_out;     // nobody observes the last gradient and update
         float* const gsave = last ? r.grad_out : nullptr;

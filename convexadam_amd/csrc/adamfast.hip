@@ -210,7 +210,7 @@ typedef AdamConsts AdamFastConsts;
 __device__ __forceinline__ void adam_update_fast(float g, float& P, float& m, float& v, const AdamFastConsts& ac) { adam_update(g, P, m, v, ac); }
 static AdamFastConsts adam_fast_consts(double bc1, double bc2) {
     const double beta1 = 0.9, beta2 = 0.999;
-    return AdamFastConsts{(float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)sqrt(bc2), (float)(-(1.0 / bc1)), nullptr};
+    return AdamFastConsts{(float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), const_div_ieee((float)sqrt(bc2)), (float)(-(1.0 / bc1)), nullptr};      // (the fast modes keep the IEEE division)
 }
 
 // One workgroup = one channel x one TZ x TY x TX output tile (TX = 4 TXQ - 8); input region: 3 planes / rows of halo and one aligned

@@ -325,8 +325,7 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_box3_tile(const float* __restr
                     float* Pc = P + (size_t)c * V + o; float* mc = m + (size_t)c * V + o; float* vc = v + (size_t)c * V + o;
                     const float4 p4 = *reinterpret_cast<const float4*>(Pc), m4 = *reinterpret_cast<const float4*>(mc), v4 = *reinterpret_cast<const float4*>(vc);
                     float pp[4] = {p4.x, p4.y, p4.z, p4.w}, mm[4] = {m4.x, m4.y, m4.z, m4.w}, vv[4] = {v4.x, v4.y, v4.z, v4.w};
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) adam_update(fin[j], pp[j], mm[j], vv[j], ac);
+                    adam_update_n<4>(fin, pp, mm, vv, ac);
                     if (WT) {
                         global_store16_wt(Pc, make_float4(pp[0], pp[1], pp[2], pp[3]));
                         global_store16_wt(mc, make_float4(mm[0], mm[1], mm[2], mm[3]));

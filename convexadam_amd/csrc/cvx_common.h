@@ -271,6 +271,34 @@ __device__ __forceinline__ float div_exact(float x) {
 template <int D>
 __device__ __forceinline__ float div_exact_inf(float x) { return __builtin_isinf(x) ? x : div_exact<D>(x); }
 
+// The same three operations for a divisor that is a launch argument: x / cd.d, bit for bit.  The host proves a divisor once by enumeration
+// (constdiv.hip: const_div_make, and there the argument why one binade of x stands for 2^-76 <= |x| <= 2^76); cd.ok = 0 -- divisor not
+// proven, or outside 2^-48 <= d < 2^49 -- keeps the IEEE division.  So does every x outside that guard: +-0 (the sequence would lose the
+// sign of -0.0), denormal and huge values, Inf and NaN.  Both tests are wave-uniform branches -- cd.ok is a kernel argument, and ONE lane
+// outside the guard sends its whole wavefront down the IEEE path -- so the common path carries the compares and no select.
+struct ConstDiv { float d, r; int ok; };
+constexpr float kConstDivLo = 0x1p-76f, kConstDivHi = 0x1p76f;
+ConstDiv const_div_ieee(float d);               // {d, 1 / d, 0}: the IEEE division, nothing proven
+ConstDiv const_div_make(float d);               // proves d now (host cost: constdiv.hip); uncached
+ConstDiv const_div(float d);                    // the same through the process-wide table of proofs (thread-safe)
+ConstDiv const_div_if_proven(float d);          // the table's entry, or const_div_ieee(d): never enumerates
+bool const_div_enumerate(float d, float r);      // the proof itself: true when x * r corrected twice equals x / d on all of [1, 2)
+void const_div_prove(const float* ds, int n, int budget);      // proves up to `budget` of the divisors the table lacks, on up to 8 threads
+__device__ __forceinline__ float div_const_seq(float x, const ConstDiv& cd) {
+    const float q = x * cd.r;
+    const float e = __builtin_fmaf(-cd.d, q, x);
+    return __builtin_fmaf(e, cd.r, q);
+}
+__device__ __forceinline__ bool div_const_inside(float x) { const float a = __builtin_fabsf(x); return a >= kConstDivLo && a <= kConstDivHi; }
+// for dividends known to be +0, at least 2^-76, +Inf or NaN (a square root): +0 / d = +0 is what the sequence gives, so only the top is tested
+__device__ __forceinline__ bool div_const_inside_root(float x) { return x <= kConstDivHi; }
+// true when `inside` holds on every active lane of the wavefront
+__device__ __forceinline__ bool wave_all(bool inside) { return __builtin_amdgcn_ballot_w64(!inside) == 0; }
+__device__ __forceinline__ float div_const(float x, const ConstDiv& cd) {
+    if (cd.ok && wave_all(div_const_inside(x))) return div_const_seq(x, cd);
+    return fdiv(x, cd.d);
+}
+
 // ATen outer-dimension sum order over `n` values held in registers (see oracle outer_sum_rows):
 // plain sequential cascade (level step 16) or, for the last (ncols mod 32) columns, the 4-way
 // interleaved `row_sum` order.  n is a compile-time constant at every call site that matters.
@@ -429,7 +457,9 @@ int launch_resize2(const float* in, int C, int h, int w, int d, int H, int W, in
 // beside it, as a function of (exponent parity, mantissa)): two bits per class, 0 = IEEE root, 1 = one ulp above, 2 = one ulp below;
 // entries 0 .. 2^24-1 normal inputs, key = exponent parity << 23 | mantissa; entries 2^24 .. 2^24+2^23-1 denormal inputs, key =
 // mantissa; 16 entries per 32-bit word, low bits first (cvx_set_adam_sqrt_table).  nullptr (default): IEEE sqrt.
-struct AdamConsts { float w1, b2, omb2, bc2s, neg_step; const unsigned* sqrt_tbl; };
+// bc2s = (float)sqrt(1 - beta2^step), one value per launch, as a ConstDiv: the division by it takes div_const's three operations when the
+// host has proven that value (adam_run_impl), the IEEE sequence otherwise; the division by the denominator varies per element and stays IEEE
+struct AdamConsts { float w1, b2, omb2; ConstDiv bc2s; float neg_step; const unsigned* sqrt_tbl; };
 __device__ __forceinline__ float adam_sqrt(float x, const unsigned* __restrict__ tbl) {
     float r = fsqrt(x);
     if (tbl) {
@@ -445,14 +475,41 @@ __device__ __forceinline__ float adam_sqrt(float x, const unsigned* __restrict__
 // torch.argmin's comparison inside a sequential scan: a candidate replaces the running best when it is smaller, or when it is the first NaN
 // (bitwise operators: no short-circuit branches inside the unrolled streaming loops)
 __device__ __forceinline__ bool argmin_better(float cost, float best) { return (cost < best) | ((cost != cost) & (best == best)); }
+// N elements of one lane at a time, so that the guard of div_const costs one wave-uniform branch per call and the N updates still interleave.
+// The dividend of the first division is a square root, so it is +0, a value in [2^-75, 2^64], +Inf or NaN (div_const_inside_root).  It is never
+// -0.0: vv is the rounded sum of the product (omb2 g) g, which is +0 or positive, and of v * b2, and (+0) + (-0) = +0 even if a caller's v
+// holds -0.0; the sqrt table's correction moves a non-zero root by one ulp and leaves zero alone.
+template <int N>
+__device__ __forceinline__ void adam_update_n(const float (&g)[N], float (&P)[N], float (&m)[N], float (&v)[N], const AdamConsts& ac) {
+    float root[N];
+    bool inside = true;
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+        m[j] = __builtin_fmaf(ac.w1, g[j] - m[j], m[j]);            // exp_avg.lerp_(grad, 1-beta1)
+        float vv = v[j] * ac.b2;                                     // exp_avg_sq.mul_(beta2)
+        vv = __builtin_fmaf(ac.omb2 * g[j], g[j], vv);               // .addcmul_(grad, grad, value=1-beta2)
+        v[j] = vv;
+        root[j] = adam_sqrt(vv, ac.sqrt_tbl);
+        inside &= div_const_inside_root(root[j]);
+    }
+    if (ac.bc2s.ok && wave_all(inside)) {
+#pragma unroll
+        for (int j = 0; j < N; ++j) root[j] = div_const_seq(root[j], ac.bc2s);
+    } else {
+#pragma unroll
+        for (int j = 0; j < N; ++j) root[j] = fdiv(root[j], ac.bc2s.d);
+    }
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+        const float den = root[j] + 1e-8f;                          // (sqrt / bias_correction2_sqrt).add_(eps)
+        P[j] = P[j] + fdiv(ac.neg_step * m[j], den);                 // addcdiv_(exp_avg, denom, value=-step_size)
+    }
+}
 __device__ __forceinline__ void adam_update(float g, float& P, float& m, float& v, const AdamConsts& ac) {
-    const float mm = __builtin_fmaf(ac.w1, g - m, m);            // exp_avg.lerp_(grad, 1-beta1)
-    float vv = v * ac.b2;                                         // exp_avg_sq.mul_(beta2)
-    vv = __builtin_fmaf(ac.omb2 * g, g, vv);                      // .addcmul_(grad, grad, value=1-beta2)
-    const float den = fdiv(adam_sqrt(vv, ac.sqrt_tbl), ac.bc2s) + 1e-8f;   // (sqrt / bias_correction2_sqrt).add_(eps)
-    P = P + fdiv(ac.neg_step * mm, den);                          // addcdiv_(exp_avg, denom, value=-step_size)
-    m = mm;
-    v = vv;
+    const float g1[1] = {g};
+    float P1[1] = {P}, m1[1] = {m}, v1[1] = {v};
+    adam_update_n<1>(g1, P1, m1, v1, ac);
+    P = P1[0]; m = m1[0]; v = v1[0];
 }
 // adam.hip: the Adam loop behind the cvx_adam_run_* entry points and the whole-pair pipeline.  One argument bundle, filled by name: the 24
 // arguments of cvx_adam_run_f32 (include/convexadam_hip.h), then what the callers differ in
@@ -465,6 +522,7 @@ struct AdamRun {
     bool f16_features = false;             // the loop's feature records in half precision
     int fast = 0;                          // 0 exact, 1 fast, 2 fast_all
     bool features_are_records = false;     // F2 / M2 already hold the chunked records
+    bool ieee_div = false;                 // tests only (cvx_adam_run_mode_f32, mode + 32): every ConstDiv of the run with ok = 0
 };
 int adam_run_impl(const AdamRun& r);
 size_t adam_record_floats(int C, size_t V);            // floats of one feature record of the Adam loop: [CP/4][V + 1][4], CP = C rounded up to 4
@@ -547,7 +605,8 @@ int launch_box3_tile(const float* in, float* out, int h, int w, int d, int varia
 // (half: records of four half-precision values -- fp16 storage of the pooled features -- instead of four floats)
 int launch_to_chunked(const float* in, int C, size_t V, float* out, bool half, hipStream_t s);
 int launch_warp_grad(const float* Fcl, const float* Mcl, int C, int h, int w, int d, const float* U, const float* bh,
-                     const float* bw, const float* bd, float gsc, float cH, float cW, float cD, float* gU, bool half, bool prediv, bool wt, hipStream_t s);
+                     const float* bw, const float* bd, float gsc, float cH, float cW, float cD, float* gU, bool half, bool prediv, bool wt, bool constdiv, hipStream_t s);
+// (constdiv: the divisions by (n - 1) / 2 through div_const where the divisors are proven; false = IEEE, for the tests)
 // adamfast.hip: adam_mode "fast" -- FMA / factored warp + gradient (float32 records) and the separable adjoint boxes with the Adam
 // update in the epilogue (P != nullptr: in-place update of P, m, v with G = box(in); P == nullptr: out = box(in)); bc1, bc2 = the bias
 // corrections 1 - beta^step of this iteration

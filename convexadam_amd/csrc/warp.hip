@@ -61,7 +61,7 @@ __global__ __launch_bounds__(256) void k_warp_grad(const float* __restrict__ F2,
                                                    const float* __restrict__ bh, const float* __restrict__ bw,
                                                    const float* __restrict__ bd, float gsc, float cH, float cW, float cD,
                                                    float* __restrict__ gU, unsigned long long* __restrict__ census, FastDiv dx, FastDiv dy,
-                                                   float sc0, float sc1, float sc2) {
+                                                   ConstDiv sc0, ConstDiv sc1, ConstDiv sc2) {
     const size_t V = (size_t)h * w * d;
     if (census && threadIdx.x == 0) {                   // debugging aid (option census_ptr, tools/adam_census.py)
         census[4 * blockIdx.x] = __builtin_amdgcn_s_memrealtime();
@@ -82,9 +82,18 @@ __global__ __launch_bounds__(256) void k_warp_grad(const float* __restrict__ F2,
     if (x >= d || y >= w || z >= h) return;
     const unsigned p = (unsigned)((z * w + y) * d + x);
     // sc0 = (float)((h - 1) / 2.0), sc1, sc2 likewise: evaluated on the host (launch_warp_grad)                  (:171)
+    // The six divisions by them go through div_const's three operations when the host has proven all three divisors (sc_ok, a scalar) and
+    // no lane of the wavefront holds a dividend outside the guard -- +-0 included, so the first iteration's U = 0 takes the IEEE sequence
+    const bool sc_ok = (sc0.ok & sc1.ok & sc2.ok) != 0;
     const float uH = U[p], uW = U[V + p], uD = U[2 * V + p];
+    float qH, qW, qD;
+    if (sc_ok && wave_all(div_const_inside(uH) && div_const_inside(uW) && div_const_inside(uD))) {
+        qH = div_const_seq(uH, sc0); qW = div_const_seq(uW, sc1); qD = div_const_seq(uD, sc2);
+    } else {
+        qH = fdiv(uH, sc0.d); qW = fdiv(uW, sc1.d); qD = fdiv(uD, sc2.d);
+    }
     Tri t;
-    tri_setup(t, bd[x] + fdiv(uD, sc2), bw[y] + fdiv(uW, sc1), bh[z] + fdiv(uH, sc0), h, w, d);
+    tri_setup(t, bd[x] + qD, bw[y] + qW, bh[z] + qH, h, w, d);
     const int x0 = t.x0, y0 = t.y0, z0 = t.z0, x1 = x0 + 1, y1 = y0 + 1, z1 = z0 + 1;
     const float fx0 = (float)x0, fy0 = (float)y0, fz0 = (float)z0, fx1 = (float)x1, fy1 = (float)y1, fz1 = (float)z1;
     // Branch-free gathers: a corner outside the volume reads the all-zero record V.  ATen skips such corners; adding
@@ -143,10 +152,12 @@ __global__ __launch_bounds__(256) void k_warp_grad(const float* __restrict__ F2,
         }
     }
     // grad wrt the normalised grid (x,y,z) = (size/2)*gi ; flip ; / scale -> grad wrt U (H,W,D)
-    float g[3];
-    g[0] = fdiv(((float)h / 2.0f) * giz, sc0);
-    g[1] = fdiv(((float)w / 2.0f) * giy, sc1);
-    g[2] = fdiv(((float)d / 2.0f) * gix, sc2);
+    float g[3] = {((float)h / 2.0f) * giz, ((float)w / 2.0f) * giy, ((float)d / 2.0f) * gix};
+    if (sc_ok && wave_all(div_const_inside(g[0]) && div_const_inside(g[1]) && div_const_inside(g[2]))) {
+        g[0] = div_const_seq(g[0], sc0); g[1] = div_const_seq(g[1], sc1); g[2] = div_const_seq(g[2], sc2);
+    } else {
+        g[0] = fdiv(g[0], sc0.d); g[1] = fdiv(g[1], sc1.d); g[2] = fdiv(g[2], sc2.d);
+    }
     // Diffusion regulariser: the 18 neighbour values are fetched in one batch from clamped (always valid) addresses
     // and the one-sided terms are selected afterwards -- one memory round trip instead of 18 dependent ones.
     // (32-bit element offsets from the uniform channel base: the launcher guarantees 16 * (V + 1) < 2^32)
@@ -190,13 +201,15 @@ int launch_to_chunked(const float* in, int C, size_t V, float* out, bool half, h
 }
 
 int launch_warp_grad(const float* Fcl, const float* Mcl, int C, int h, int w, int d, const float* U, const float* bh,
-                     const float* bw, const float* bd, float gsc, float cH, float cW, float cD, float* gU, bool half, bool prediv, bool wt, hipStream_t s) {
+                     const float* bw, const float* bd, float gsc, float cH, float cW, float cD, float* gU, bool half, bool prediv, bool wt, bool constdiv, hipStream_t s) {
     const int CP = (C + 3) / 4 * 4;
     const dim3 gv((unsigned)((cdiv(d, 16) * cdiv(w, 4) * cdiv(h, 4) + 7) / 8 * 8));     // multiple of the 8 XCDs
     unsigned long long* census = reinterpret_cast<unsigned long long*>(options().census_ptr);       // debugging aid: slots [8192, ..)
     if (census) census += 8 * 1024;
     const FastDiv dx = fastdiv_make(cdiv(d, 16)), dy = fastdiv_make(cdiv(w, 4));
-    const float sc0 = (float)((h - 1) / 2.0), sc1 = (float)((w - 1) / 2.0), sc2 = (float)((d - 1) / 2.0);
+    // (the first launch on a grid proves its three divisors, host cost: constdiv.hip; later ones find them in the table)
+    auto scale = [&](int n) { const float sc = (float)((n - 1) / 2.0); return constdiv ? const_div(sc) : const_div_ieee(sc); };
+    const ConstDiv sc0 = scale(h), sc1 = scale(w), sc2 = scale(d);
 #define CVX_WG_LAUNCH(...) hipLaunchKernelGGL((k_warp_grad<__VA_ARGS__>), gv, dim3(256), 0, s, Fcl, Mcl, C, CP, h, w, d, U, bh, bw, bd, gsc, cH, cW, cD, gU, census, dx, dy, sc0, sc1, sc2)
 #define CVX_WG_WT(B, H, D) do { if (wt) CVX_WG_LAUNCH(B, H, D, true); else CVX_WG_LAUNCH(B, H, D, false); } while (0)
     if (half) { if (prediv) CVX_WG_WT(true, true, true); else CVX_WG_WT(true, true, false); }

@@ -370,6 +370,22 @@ int cvx_adam_run_mode_f32(const float* F2, const float* M2, int C, int h, int w,
                           const float* base_h, const float* base_w, const float* base_d, float* U, float* grad_out,
                           const int* snapshot_iters_host, int n_snap, float* snapshots, const cvx_smoother* sm, int mode,
                           void* workspace, size_t workspace_bytes, void* stream);
+/* (tests only: mode + 32 runs the exact loop with the IEEE division everywhere, that is with no divisor treated as proven -- see below) */
+/* Division by a launch-constant divisor in three operations (q = x r, e = fma(-d, q, x), q' = fma(e, r, q), r = RN(1 / d)): the exact
+ * Adam loop uses it for its divisions by (n - 1) / 2 and by sqrt(1 - beta2^step) where the host has PROVEN the divisor -- the sequence
+ * equals x / d bit for bit for every x with 2^-76 <= |x| <= 2^76, by enumeration of one binade (csrc/constdiv.hip) -- and the IEEE
+ * sequence for every other divisor and dividend.  Host only, no device needed: r and ok (1 = proven) of a divisor; cached != 0 goes
+ * through the process-wide table of proofs the loop itself uses (thread-safe). */
+int cvx_const_div_make(float d, int cached, float* r, int* ok);
+/* A run proves the divisors of its own steps before it enqueues its first kernel, at most 128 new ones per call: a first run of more
+ * iterations keeps the IEEE division for the rest until a later call has proven them (same results, a few percent slower), and a launch
+ * that was captured and is replayed keeps the choice it was captured with. */
+/* tests only: 1 when the enumeration accepts divisor d with reciprocal r (any r: one that is off by 2^-8 has to be refused) */
+int cvx_const_div_enumerate(float d, float r);
+/* counts the x of both signs with biased exponents exp_lo .. exp_hi (0 = denormals and zero .. 254) for which the three operations
+ * (guarded != 0: with the IEEE fallback outside 2^-76 <= |x| <= 2^76, as on the device) differ from x / d; first_bad (may be NULL)
+ * receives the first such bit pattern; -1 for a bad exponent range.  One float at a time, independent of cvx_const_div_make. */
+long long cvx_const_div_mismatches(float d, int exp_lo, int exp_hi, int guarded, unsigned* first_bad);
 /* separable restatement of a box-chain smoother (kovesi_spline, hyper_util:475-488) on a [3][h][w][d] field: per axis the boxes of the
  * chain as 1-D sums with zero padding per stage, `backward` = the adjoint (reversed box order), one final multiplication by
  * 1 / prod k^3; in == out allowed.  Equals cvx_smooth_f32 to rounding (3e-7 relative), three launches instead of one per box and 27 /
