@@ -170,6 +170,7 @@ SIGNATURES = {
     "cvx_field_to_grid_f64": (_i, [_vp, _i, _i64, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     "cvx_field_mean_workspace_bytes": (_sz, [_i] * 3),
     "cvx_field_mean_f64": (_i, [_vp, _i, C.c_longlong, C.c_longlong, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "cvx_crop_field_half_f32": (_i, [_vp, _i64, _i64, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
 }
 
 _lib = None

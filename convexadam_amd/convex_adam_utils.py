@@ -492,3 +492,6 @@ from .rigid import convex_adam_rigid, convex_stage, label_centroids, landmark_tr
 # physical-space resampling and field carry-over on the device (convex_adam_utils.py:282-351, apply_convex.py:27-78): csrc/geometry.hip
 from .geometry import (Grid, field_mean_device, grid_of, index_map, register_images, resample_device,  # noqa: E402,F401
                        rescale_displacement_field_device)
+# a cropped-grid field carried to the original fixed grid at half resolution (l2r_2021_convexAdam_task1_docker.py:38-105,390-400): csrc/cropfield.hip
+from .cropfield import (CropCase, convert_crop_field, half_resolution_field, physical_displacement, read_cases,  # noqa: E402,F401
+                        submission_field)

@@ -713,6 +713,51 @@ int cvx_field_mean_f64(const void* field, int field_is_f64, long long comp_strid
                        const unsigned char* mask, const void* seg, int seg_kind, int sH, int sW, int sD, const double* map12, double* sums3,
                        long long* count, void* workspace, size_t workspace_bytes, void* stream);
 
+/* A cropped-grid field carried to the original fixed grid at half resolution (csrc/cropfield.hip) ---------------------------------------
+ * replaces l2r_2021_convexAdam_task1_docker.py:390-397 (voxel field -> displacement in millimetres) and convert_crop_field (:38-105):
+ * the chain through two crop affines and two spacings with a border-clamped grid_sample(align_corners=True), the axis flips with their
+ * sign change, F.interpolate(scale_factor=0.5, trilinear, align_corners=False) and the cast to float16 -- in one launch that writes
+ * nothing but the half-resolution result.  With CVX_CROP_IDENTITY it is the plain halving that ends task2:308-315 and task3:213-217.
+ *   field    component a (0, 1, 2 = along array axis 0, 1, 2) of voxel q = (i0 W + i1) D + i2 of the registration grid [H][W][D] at
+ *            field[a * comp_stride + q * voxel_stride] (float elements), read in place; the strides as in cvx_field_to_grid_f64:
+ *            (H W D, 1) = [3][H][W][D] as cvx_register_pair_f32 gives it, (1, 3) = [H][W][D][3] as the reference's disp_p is laid out.
+ *   geom27_host (HOST, 9 triples of doubles, one value per axis): fix_scale, fix_crop_lo, new_fix_spacing, new_mov_spacing, mov_scale,
+ *            mov_crop_lo, pre_fix_spacing, pre_mov_spacing, fix_crop_hi.  The first eight enter the arithmetic; fix_crop_hi only the check
+ *            rint(fix_scale_a (fix_crop_hi_a - fix_crop_lo_a)) == (H, W, D)_a.  NULL only with CVX_CROP_IDENTITY.
+ *   flip_mask bit a set: output index i along axis a reads source index S_a - 1 - i, and component a is negated (the reference: 'xy' = 3).
+ *   flags    CVX_CROP_FIELD_VOXELS  the field is a displacement in voxels of the registration grid, and every tap y = (y_0, y_1, y_2) is
+ *                                   turned into millimetres as it is read: v_a = (y_a + u_a(y)) * pre_mov_spacing_a - y_a * pre_fix_spacing_a
+ *                                   in FLOAT, every operation rounded, the two spacings rounded to float first -- the reference's own
+ *                                   float32 disp_p (task1:393-397), so the launch gives the bits of one on that materialised field;
+ *                                   without the flag the field is that physical disp_p already and v_a = u_a(y)
+ *            CVX_CROP_OUT_F32       out is float instead of half precision
+ *            CVX_CROP_IDENTITY      no chain: (H, W, D) must equal (S0, S1, S2), and d_a(x) = field_a(x)
+ *   out      [3][S0 / 2][S1 / 2][S2 / 2] (integer division), half precision or float.
+ * Per voxel x = (x_0, x_1, x_2) of the original fixed grid [S0][S1][S2] and per axis a, in float64 with plain multiplies, adds and IEEE
+ * divisions in exactly this order (the file is compiled without contraction):
+ *     g_a = fix_scale_a * (x_a - fix_crop_lo_a)
+ *     c_a = g_a > 0 ? g_a : 0;  c_a = c_a > n_a - 1 ? n_a - 1 : c_a            (n = (H, W, D); a NaN fails the first comparison: 0)
+ *     f = floor(c_a), t = c_a - f, taps {(int) f, min((int) f + 1, n_a - 1)}, weights {1 - t, 1 - (1 - t)}
+ *     p_a = sum over the 8 taps, axis 0 slowest, of ((v_a * w_0) * w_1) * w_2, started from 0.0          (v_a as under `flags`)
+ *     m_a = ((g_a * new_fix_spacing_a + p_a) / new_mov_spacing_a) / mov_scale_a + mov_crop_lo_a
+ *     d_a = m_a - x_a, negated when bit a of flip_mask is set, rounded to float (nearest even)
+ * Output voxel o takes, per axis, the taps 2 o and min(2 o + 1, S - 1) of the flipped grid, weights 0.5 and 0.5 -- ATen under
+ * scale_factor = 0.5, NOT under size = S / 2 -- combined in float in ATen's order, last axis first:
+ *     r_jk = d[j][k][0] * 0.5 + d[j][k][1] * 0.5;   s_j = r_j0 * 0.5 + r_j1 * 0.5;   value = s_0 * 0.5 + s_1 * 0.5
+ * The float output is that value; the half-precision output is its round-to-nearest-even cast (inf beyond 65504), so the two outputs of
+ * the same input agree through one cast.  In identity mode the result is F.interpolate(scale_factor=0.5, mode='trilinear') bit for bit.
+ * One thread produces four consecutive outputs along the last axis and stores them per component plane in one 8-byte (half) or 16-byte
+ * (float) access where that address is so aligned, element by element otherwise.  No workspace, no atomics.
+ * CVX_ERR_INVALID_ARG before anything is launched: NULL field, out or (without CVX_CROP_IDENTITY) geom27_host; out not aligned to its
+ * element; out overlapping the field; an extent below 1, or an S below 2 (empty output); more than 2^31 - 1 voxels on either grid; a
+ * non-finite entry in geom27_host, a zero scale or spacing; strides that fold the components onto each other; flip_mask outside 0..7 or an
+ * unknown flag; a registration grid that is not the case's (H, W, D); CVX_CROP_IDENTITY together with CVX_CROP_FIELD_VOXELS. */
+#define CVX_CROP_FIELD_VOXELS 1
+#define CVX_CROP_OUT_F32 2
+#define CVX_CROP_IDENTITY 4
+int cvx_crop_field_half_f32(const float* field, int64_t comp_stride, int64_t voxel_stride, int H, int W, int D, const double* geom27_host,
+                            int S0, int S1, int S2, int flip_mask, int flags, void* out, void* stream);
+
 #pragma GCC visibility pop
 
 #ifdef __cplusplus
