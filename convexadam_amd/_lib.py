@@ -171,6 +171,8 @@ SIGNATURES = {
     "cvx_field_mean_workspace_bytes": (_sz, [_i] * 3),
     "cvx_field_mean_f64": (_i, [_vp, _i, C.c_longlong, C.c_longlong, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "cvx_crop_field_half_f32": (_i, [_vp, _i64, _i64, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "cvx_ranksum_critical_u2": (_i, [_i, C.c_double, C.POINTER(C.c_int)]),
+    "cvx_ranksum_better_f64": (_i, [_vp, _vp, C.c_double, C.c_double, _i, _i, _i, _i, _vp, _vp, _vp]),
 }
 
 _lib = None

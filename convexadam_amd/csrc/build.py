@@ -11,7 +11,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-SOURCES = ["api.hip", "mind.hip", "mindmarch.hip", "pool.hip", "labelpool.hip", "correlate.hip", "corrbox.hip", "corrfused.hip", "corrcert.hip", "certify.hip", "convex.hip", "adam.hip", "constdiv.hip", "adamfast.hip", "warp.hip", "boxmarch.hip", "boxtile.hip", "metrics.hip", "edt.hip", "surfdist.hip", "pipeline.hip", "tps.hip", "rigid.hip", "rigidreg.hip", "ssim.hip", "geometry.hip", "fieldmean.hip", "cropfield.hip"]
+SOURCES = ["api.hip", "mind.hip", "mindmarch.hip", "pool.hip", "labelpool.hip", "correlate.hip", "corrbox.hip", "corrfused.hip", "corrcert.hip", "certify.hip", "convex.hip", "adam.hip", "constdiv.hip", "adamfast.hip", "warp.hip", "boxmarch.hip", "boxtile.hip", "metrics.hip", "edt.hip", "surfdist.hip", "pipeline.hip", "tps.hip", "rigid.hip", "rigidreg.hip", "ssim.hip", "geometry.hip", "fieldmean.hip", "cropfield.hip", "ranksum.hip"]
 PER_FILE_FLAGS = {"warp.hip": ["-fno-slp-vectorize"], "adamfast.hip": ["-fno-slp-vectorize"], "boxmarch.hip": ["-fno-slp-vectorize"], "boxtile.hip": ["-fno-slp-vectorize"], "corrbox.hip": ["-fno-slp-vectorize"], "corrfused.hip": ["-fno-slp-vectorize"], "corrcert.hip": ["-fno-slp-vectorize"], "mindmarch.hip": ["-fno-slp-vectorize"], "ssim.hip": ["-fno-slp-vectorize"]}     # see the header of warp.hip
 LIB = os.path.join(HERE, "libconvexadam_hip.so")
 OBJDIR = os.path.join(HERE, "build")

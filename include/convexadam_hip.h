@@ -758,6 +758,38 @@ int cvx_field_mean_f64(const void* field, int field_is_f64, long long comp_strid
 int cvx_crop_field_half_f32(const float* field, int64_t comp_stride, int64_t voxel_stride, int H, int W, int D, const double* geom27_host,
                             int S0, int S1, int S2, int flip_mask, int flags, void* out, void* stream);
 
+/* Rank-sum tests of every ordered pair of N teams (csrc/ranksum.hip) -------------------------------------------------------------------------
+ * replaces the scipy.stats.ranksums loop of self_configuring/l2r3.py:262-271 (`scores_better`): for teams i, j with S samples each
+ * (n1 = n2 = S, no tie correction) scipy computes, in float64,
+ *     U2 = 2 #{a > b} + #{a == b}                       over a in x_i, b in x_j, IEEE comparisons
+ *     s = U2 / 2 + S (S + 1) / 2                        the rank sum of x_i with average ranks: a half-integer, exact
+ *     z = (s - S (2 S + 1) / 2) / sqrt(S S (2 S + 1) / 12)
+ *     p = 2 norm.sf(|z|) = erfc(|z| / sqrt(2))
+ * and the reference keeps better[i][j] = (z > 0) & (p < p_threshold).  z grows with U2, so that is U2 >= u2_crit for one integer per S.
+ *
+ * cvx_ranksum_critical_u2 (HOST only, no device): *u2_crit = the smallest U2 in (S^2, 2 S^2] with z > 0 and erfc(|z| / sqrt(2)) <
+ * p_threshold, z in float64 in exactly the order above and erfc from libm; 2 S^2 + 1 ("never") when no value qualifies (S = 1 and S = 2
+ * at 0.05).  CVX_ERR_INVALID_ARG: a null pointer, S < 1, S > 4096, p_threshold outside (0, 1) or NaN.
+ *
+ * cvx_ranksum_better_f64:
+ *   samples  [R][N][S] doubles on the device: R independent repeats
+ *   means    NULL, or [N] floats on the device.  With means the sample compared is
+ *                x = sign * ((double) mean_i + scale * samples[r][i][k])
+ *            the product rounded, then the sum, then the sign (no contraction): the reference's sign * (mean.reshape(N, -1) +
+ *            .1 * randn(N, N)) with float32 means.  With NULL, x = samples[r][i][k] and scale and sign are ignored.
+ *   scores   [R][N] ints: scores[r][j] = sum over i of [U2(r, i, j) >= u2_crit] -- the column sum of `better`: how many teams are
+ *            significantly greater than team j
+ *   u2       NULL, or [R][N][N] ints: the raw U2(r, i, j)
+ * A NaN compares false both ways: a NaN sample adds nothing to any U2, so a team of NaNs is never better and nothing is better than it
+ * (scipy's propagated NaN decides the same).  -0.0 == 0.0; +-inf are ordinary values.  u2_crit = 0 counts every pair (scores = N),
+ * 2 S^2 + 1 none.  One work-group per (r, j); scores and u2 are each written once by plain vector stores; no atomics, no workspace.
+ * CVX_ERR_INVALID_ARG before anything is launched: NULL samples or scores; R, N or S below 1; N or S above 4096; R N S, or R N N when u2
+ * is given, above 2^31 - 1; u2_crit outside [0, 2 S^2 + 1]; a non-finite scale or sign when means is given; a buffer not aligned to its
+ * element; scores, u2, samples or means overlapping. */
+int cvx_ranksum_critical_u2(int S, double p_threshold, int* u2_crit);
+int cvx_ranksum_better_f64(const double* samples, const float* means, double scale, double sign, int R, int N, int S, int u2_crit, int* scores,
+                           int* u2, void* stream);
+
 #pragma GCC visibility pop
 
 #ifdef __cplusplus
