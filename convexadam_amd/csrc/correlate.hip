@@ -28,6 +28,7 @@ struct CorrGeom {
     int PL;     // left pad of Mp rows (multiple of 4, >= hw)
     int dq;     // Mp row pitch: element x at index x + PL + 1
     int hq, wq; // Mp plane extents (h+2hw, w+2hw)
+    int mpad;   // floats behind Mp that a 16-byte load of the fused kernel may cover (cf_layout carves 8): written as zeros; 0 = none
 };
 static CorrGeom corr_geom(int C, int h, int w, int d, int hw) {
     CorrGeom g;
@@ -36,6 +37,7 @@ static CorrGeom corr_geom(int C, int h, int w, int d, int hw) {
     g.PL = (hw + 3) / 4 * 4;
     g.dq = g.px + 2 * g.PL;
     g.hq = h + 2 * hw; g.wq = w + 2 * hw;
+    g.mpad = 0;
     return g;
 }
 
@@ -54,7 +56,7 @@ __global__ __launch_bounds__(256) void k_corr_prep(const float* __restrict__ fix
         const int x = xq - g.PL - 1, y = yq - g.hw, z = zq - g.hw;
         const bool in = x >= 0 && x < g.d && y >= 0 && y < g.w && z >= 0 && z < g.h;
         Mp[i] = in ? mov[(((size_t)c * g.h + z) * g.w + y) * g.d + x] : 0.0f;
-    }
+    } else if (i < nM + (size_t)g.mpad) Mp[i] = 0.0f;
 }
 
 // ---- raw SSD: register tile of 4 row indices x n D-shifts ---------------------------------------------
@@ -219,8 +221,8 @@ __global__ void k_corr_tail_compact(const float* __restrict__ fix, const float* 
 void launch_corr_prep_generic(const float* fix, const float* mov, int C, int h, int w, int d, int hw, int px, int PL, int dq, float* Fp,
                               float* Mp, hipStream_t s) {
     CorrGeom g = corr_geom(C, h, w, d, hw);
-    g.px = px; g.PL = PL; g.dq = dq;
-    const size_t nprep = std::max((size_t)C * g.hq * g.wq * g.dq, (size_t)C * h * w * g.px);
+    g.px = px; g.PL = PL; g.dq = dq; g.mpad = 8;
+    const size_t nprep = std::max((size_t)C * g.hq * g.wq * g.dq + g.mpad, (size_t)C * h * w * g.px);
     hipLaunchKernelGGL(k_corr_prep, dim3((unsigned)cdiv64((int64_t)nprep, 256)), dim3(256), 0, s, fix, mov, g, Fp, Mp);
 }
 

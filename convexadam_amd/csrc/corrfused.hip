@@ -519,14 +519,16 @@ int corr_fused_items(int C, int h, int w, int d, int hw) { return corr_fused_sup
 
 bool corr_fused_tiled(int C, int h, int w, int d, int hw) { return cf_geom(C, h, w, d, hw).tiled != 0; }
 
-// one direction's padded feature copies and tail values, then the residency census of option cf_census (+ 8: the 512 slots of option cf_map)
+// one direction's padded feature copies and tail values, then the residency census of option cf_census: four words per WORKGROUP of the
+// launch -- one per item, or the fixed 512 of the co-located launch (option cf_map = 1), which exceed the items of hw = 5 (363)
+static int cf_census_slots(const CFGeom& g) { const int n = cf_items(g) + 8; return n > 512 ? n : 512; }
 struct CFWs { float *Fp, *Mp, *tail; unsigned long long* census; };
 static CFWs cf_layout(Carver& cv, const CFGeom& g, int C, int h, int w) {
     CFWs f;
     f.Fp = cv.take<float>((size_t)C * h * w * g.RS);
     f.Mp = cv.take<float>((size_t)C * g.hq * g.wq * g.dq + 8);
     f.tail = cv.take<float>((size_t)32 * g.n);
-    f.census = cv.take<unsigned long long>((size_t)4 * (cf_items(g) + 8));
+    f.census = cv.take<unsigned long long>((size_t)4 * cf_census_slots(g));
     return f;
 }
 size_t corr_fused_workspace_bytes(int C, int h, int w, int d, int hw) { Carver m; cf_layout(m, cf_geom(C, h, w, d, hw), C, h, w); return ws_query(m); }

@@ -2,7 +2,11 @@
 
 For each operator, shape and layout-changing option: a call with EXACTLY the queried size -- cut from the front of a larger buffer whose
 tail holds a byte pattern -- succeeds, leaves the pattern intact and produces the same bits as a call with a generous workspace; a call
-with one byte less is refused with CVX_ERR_WORKSPACE and leaves the outputs untouched.  Every input is a real allocation."""
+with one byte less is refused with CVX_ERR_WORKSPACE and leaves the outputs untouched.  Every input is a real allocation.
+
+The two workspaces also differ in what they hold when the call starts: zeros in the generous one, 0xFF bytes in the exact one.  The
+package's workspace is grow-only and shared by every operator of a thread and stream, so a call always finds another kernel's leftovers;
+equal outputs say that no entry point reads a workspace word before it has written it."""
 import ctypes as C
 
 import numpy as np
@@ -56,9 +60,11 @@ def as_bytes(t):
 
 def check_workspace(L, need, call, outs, prep=lambda: None):
     """need: the size query's value; call(ws, nbytes) -> rc; outs: every buffer the call writes; prep(): resets in/out buffers."""
-    def run(ws, nbytes):
+    def run(ws, nbytes, stale=None):
         for o in outs:
             as_bytes(o).fill_(0xA5)
+        if stale is not None:
+            stale[0].fill_(stale[1])            # what another operator might have left in the shared, grow-only workspace
         prep()
         torch.cuda.synchronize()
         before = [o.clone() for o in outs]
@@ -67,12 +73,14 @@ def check_workspace(L, need, call, outs, prep=lambda: None):
         return rc, before
 
     big = torch.empty(need + (1 << 20), dtype=torch.uint8, device=DEV)
-    rc, _ = run(p(big), big.numel())
+    rc, _ = run(p(big), big.numel(), (big, 0x00))
     assert rc == 0, L.cvx_last_error()
     ref = [o.clone() for o in outs]
     buf = torch.empty(need + TAIL, dtype=torch.uint8, device=DEV)
     buf[need:].fill_(0x5A)
-    rc, _ = run(p(buf), need)
+    # stale contents: zeros in the generous run, 0xFF bytes here (NaN as floats, -1 as counters, tickets and flags; DESIGN.md section 29 lists
+    # who initialises each such word) -- equal outputs then also say that no entry point depends on what its workspace held
+    rc, _ = run(p(buf), need, (buf[:need], 0xFF))
     assert rc == 0, L.cvx_last_error()
     assert bool((buf[need:] == 0x5A).all()), "the call wrote behind its queried workspace"
     for o, r in zip(outs, ref):
@@ -164,6 +172,37 @@ def test_correlate(L, shape, C_, fast, opts):
             return
         check_workspace(L, need, lambda ws, n: L.cvx_correlate_ex_f32(p(fix), p(mov), C_, h, w, d, hw, C.byref(co), p(ssd), p(am), ws, n, stream()),
                         [ssd, am])
+
+
+@pytest.mark.parametrize("shape", CORR_SHAPES)
+@pytest.mark.parametrize("cf_map", [0, 1])
+def test_correlate_census_hw5(L, shape, cf_map):
+    """hw = 5 is the one search width at which the co-located launch of the fused kernel (option cf_map = 1, 512 workgroups) has more
+    workgroups than items (11 * 11 * 3 = 363): with option cf_census every workgroup that passes the pair test -- up to number 376 --
+    writes its four census words.  The census is the last carve of the fused kernel's part of the workspace; behind it lie the 256 bytes
+    of slack that every size query adds and then the argmin keys (8 bytes per voxel), which the argmin pass arms after the kernel.  A
+    carve of items + 8 slots ended 192 bytes short of the last record's end: the overhang stayed inside that slack, so neither the keys
+    nor the tail pattern could show it; the carve now holds a slot per workgroup.  This test therefore could not have failed on the old carve:
+    what it pins is that the census, at the one width where it has more writers than items, changes neither the volume nor the argmin
+    and keeps the workspace contract."""
+    h, w, d = shape
+    hw, C_ = 5, 12
+    K, v = (2 * hw + 1) ** 3, h * w * d
+    fix, mov = rnd((C_,) + shape, 31), rnd((C_,) + shape, 32)
+    ssd = torch.empty(K * v, device=DEV)
+    am = torch.empty(v, dtype=torch.int64, device=DEV)
+    with option(L, cf_map=cf_map):
+        need = L.cvx_correlate_workspace_bytes(C_, h, w, d, hw)
+        plain = torch.empty(need, dtype=torch.uint8, device=DEV)
+        assert L.cvx_correlate_f32(p(fix), p(mov), C_, h, w, d, hw, p(ssd), p(am), p(plain), need, stream()) == 0, L.cvx_last_error()
+        torch.cuda.synchronize()
+        want = [ssd.clone(), am.clone()]
+        with option(L, cf_census=1):
+            assert L.cvx_correlate_workspace_bytes(C_, h, w, d, hw) == need           # the census is always carved
+            check_workspace(L, need, lambda ws, n: L.cvx_correlate_f32(p(fix), p(mov), C_, h, w, d, hw, p(ssd), p(am), ws, n, stream()), [ssd, am])
+            assert L.cvx_correlate_f32(p(fix), p(mov), C_, h, w, d, hw, p(ssd), p(am), p(plain), need, stream()) == 0, L.cvx_last_error()
+            torch.cuda.synchronize()
+    assert torch.equal(ssd, want[0]) and torch.equal(am, want[1]), "the census changed the volume or the argmin"
 
 
 @pytest.mark.parametrize("shape", CORR_SHAPES)
