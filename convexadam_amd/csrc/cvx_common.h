@@ -533,12 +533,7 @@ int coupled_convex_impl(const void* ssd, bool f16, const int64_t* argmin, const 
 int coupled_convex_dual_impl(const void* ssdA, const int64_t* argminA, float* outA, void* wsA, const void* ssdB, bool f16, const int64_t* argminB,
                              float* outB, void* wsB, const float* mesh, int h, int w, int d, int disp_hw, size_t workspace_bytes,
                              void* stream, bool counts_zeroed = false);   // counts_zeroed: the caller cleared CoupledWs::counts of both workspaces
-// mind.hip: MIND-SSC delivered only through its stride poolings (pipeline path, no full-resolution descriptor)
-bool mind_pooled_supported(int H, int W, int D, int g1, int g2);
-int launch_mind_pooled(const float* img, int H, int W, int D, int radius, int dilation, int g1, float* out1, int g2, float* out2,
-                       float* raw, void* workspace, size_t workspace_bytes, hipStream_t s, int records = 0);   // records 1 / 2: out2 = float32 / half feature records
-bool mind_pooled_records_supported(int H, int W, int D, int g1, int g2);
-size_t mind_pooled_raw_floats(int H, int W, int D, int g1, int g2);      // floats of launch_mind_pooled's `raw` scratch (>= 12 H W D: blocked tiles overhang)
+// (mind.hip's pooled descriptor and the plan of the MIND-SSC kernels: mind_common.h)
 // labelpool.hip: weighted one-hot label features delivered only through their stride poolings (g2 == 0 / out2 null: one pooling); no workspace
 int launch_label_pooled(const float* lab, int H, int W, int D, int C, const int* present, const float* weights, float mult, int g1, float* out1,
                         int g2, float* out2, hipStream_t s);

@@ -715,39 +715,72 @@ static size_t mind_lds_bytes(int R, int dil, int nbuf, int TX) {
     return sizeof(float) * ((size_t)((IZ * IY * IX + 3) / 4) * 4 + (size_t)nbuf * SZ * SY * SXP);
 }
 
-template <int R>
-static int mind_launch_r(const float* img, int H, int W, int D, int dil, MindStats* st, float* out, hipStream_t s, const MindRawLayout& lay) {
-    const bool tiled_only = options().mind_tiled != 0;
-    if (!tiled_only && mind_march_supported(img, out, H, W, D, R, dil)) {
-        launch_mind_march(img, H, W, D, st, out, s, lay);
-        return check_last("mindssc");
+// Which MIND-SSC kernels run for one use of the descriptor (DESIGN.md 30 has the table).  Everything that chooses reads this plan.
+MindPlan mind_plan(const MindUse& u) {
+    const Options& o = options();
+    MindPlan p{};
+    p.u = u;
+    const size_t V = (size_t)u.H * u.W * u.D, LDS_MAX = 160 * 1024;
+    const bool exact_mean = o.mind_mean_threads <= 0;       // the reference-bits mean walks the planar variance volume and corrects exp through a table
+    // the stencil: the z-marching kernel for radius 1, dilation 2, rows of a multiple of 4 voxels and 16-byte aligned pointers (its narrow geometry
+    // when the last 64-column tile is at most half full, option mm_tx forces one); else k_mind on tiles of 64 columns, of 32 if those exceed the LDS
+    const bool march_geo = o.mind_tiled == 0 && u.radius == 1 && u.dilation == 2 && (u.D & 3) == 0;
+    const int force = (int)o.mm_tx, rem = u.D % 64;
+    if (march_geo && u.img_aligned && u.out_aligned)
+        p.stencil = (force ? force == 32 : (rem != 0 && rem <= 32)) ? MindStencil::March16x32 : MindStencil::March8x64;
+    else if (const int tx = mind_lds_bytes(u.radius, u.dilation, 1, 64) <= LDS_MAX ? 64 : mind_lds_bytes(u.radius, u.dilation, 1, 32) <= LDS_MAX ? 32 : 0) {
+        p.stencil = tx == 64 ? MindStencil::Tiled64 : MindStencil::Tiled32;
+        p.nbuf = mind_lds_bytes(u.radius, u.dilation, 2, tx) <= LDS_MAX ? 2 : 1;
+        p.lds = mind_lds_bytes(u.radius, u.dilation, p.nbuf, tx);
     }
-    if (lay.T) return fail(CVX_ERR_UNSUPPORTED, "mindssc: the blocked layout needs the marching stencil");
-    if (mind_lds_bytes(R, dil, 1, 64) <= 160 * 1024) {
-        const dim3 grid(cdiv(D, 64), cdiv(W, TY), cdiv(H, TZ));
-        const int nbuf = mind_lds_bytes(R, dil, 2, 64) <= 160 * 1024 ? 2 : 1;
-        const size_t lds = mind_lds_bytes(R, dil, nbuf, 64);
+    // pooling: (ga, gb) = (larger, smaller) window, the larger one goes to the matching output; the second pass reads 8-byte row segments (D even)
+    p.swap = u.g2 > u.g1;
+    p.ga = p.swap ? u.g2 : u.g1; p.gb = u.g2 > 0 ? (p.swap ? u.g1 : u.g2) : u.g1;
+    const bool pair_ok = mind_pair_dispatch(p.ga, p.gb, [](auto, auto) {});
+    p.T = pair_ok && (u.D & 1) == 0 ? p.ga : 0;
+    p.records_ok = p.T != 0 && u.g2 > 0 && !p.swap;
+    p.records = p.records_ok ? u.records : 0;
+    // one pass: the marching stencil's geometry, an instantiated window pair, the library's own exp and the exactly rounded mean
+    const bool single_geo = o.mind_single != 0 && exact_mean && mind_exp_table().tbl == nullptr && pair_ok && march_geo;
+    p.single = single_geo && u.img_aligned;
+    p.single_unaligned = single_geo && !u.img_aligned;
+    p.force_repair = o.mind_single == 2;
+    // two passes: the raw SSDs blocked by the second pass's tiles when the marching kernel writes them (option mind_blocked)
+    const size_t tile = p.T ? (size_t)p.T * p.T * MP_TX : 0, ntx = cdiv(u.D, MP_TX), nty = p.T ? cdiv(u.W, p.T) : 0, ntz = p.T ? cdiv(u.H, p.T) : 0;
+    p.blocked = p.T != 0 && !p.single && o.mind_blocked != 0 && exact_mean && p.march();
+    if (p.blocked) p.lay = MindRawLayout{p.T, (int)ntx, (int)nty, 12 * tile, tile};
+    p.raw_floats = std::max(12 * V, ntx * nty * ntz * 12 * tile);
+    p.mean_threads = exact_mean ? 0 : (int)std::min<long long>(o.mind_mean_threads, 1024);
+    p.two_pass = V >= 32768 && p.mean_threads > 1;
+    p.finish4 = V % 4 == 0 && u.out_aligned;
+    return p;
+}
+
+template <int R>
+static int mind_launch_r(const MindPlan& pl, const float* img, MindStats* st, float* out, hipStream_t s) {
+    const MindUse& u = pl.u;
+    if (pl.march()) {
+        launch_mind_march(pl, img, st, out, s);
+    } else if (pl.stencil == MindStencil::Tiled64) {
         static size_t granted0 = 0;
-        ensure_dynamic_lds(&k_mind<R, 64>, lds, granted0);
-        hipLaunchKernelGGL((k_mind<R, 64>), grid, dim3(64 / RUN * TY * TZ), lds, s, img, H, W, D, dil, nbuf, st, out);
+        ensure_dynamic_lds(&k_mind<R, 64>, pl.lds, granted0);
+        hipLaunchKernelGGL((k_mind<R, 64>), dim3(cdiv(u.D, 64), cdiv(u.W, TY), cdiv(u.H, TZ)), dim3(64 / RUN * TY * TZ), pl.lds, s, img, u.H, u.W, u.D, u.dilation, pl.nbuf, st, out);
     } else {                                        // radius 3 with dilation 4: tiles of 32 columns
-        const dim3 grid(cdiv(D, 32), cdiv(W, TY), cdiv(H, TZ));
-        const int nbuf = mind_lds_bytes(R, dil, 2, 32) <= 160 * 1024 ? 2 : 1;
-        const size_t lds = mind_lds_bytes(R, dil, nbuf, 32);
         static size_t granted1 = 0;
-        ensure_dynamic_lds(&k_mind<R, 32>, lds, granted1);
-        hipLaunchKernelGGL((k_mind<R, 32>), grid, dim3(32 / RUN * TY * TZ), lds, s, img, H, W, D, dil, nbuf, st, out);
+        ensure_dynamic_lds(&k_mind<R, 32>, pl.lds, granted1);
+        hipLaunchKernelGGL((k_mind<R, 32>), dim3(cdiv(u.D, 32), cdiv(u.W, TY), cdiv(u.H, TZ)), dim3(32 / RUN * TY * TZ), pl.lds, s, img, u.H, u.W, u.D, u.dilation, pl.nbuf, st, out);
     }
     return check_last("mindssc");
 }
 
 // the MIND workspace: min / max partials and the statistics, then either the block list of the single pass (window ga > 0) or the
-// buffers of the reference-bits mean (T = option mind_mean_threads > 0): variance volume, thread slots, three cascade levels
+// buffers of the reference-bits mean (plan.mean_threads > 0): variance volume, thread slots, three cascade levels
 struct MindWs {
     float* part; MindStats* st; unsigned* blk; size_t nblk;
-    float *var, *slots, *B0, *B1, *B2; int threads; bool two_pass; long long nt, chunk, rows, s0, s1, s2;
+    float *var, *slots, *B0, *B1, *B2; long long nt, chunk, rows, s0, s1, s2;
 };
-static MindWs mind_layout(Carver& cv, int H, int W, int D, int ga, long long T) {
+static MindWs mind_layout(Carver& cv, const MindPlan& pl, int ga) {
+    const int H = pl.u.H, W = pl.u.W, D = pl.u.D;
     MindWs m{};
     m.part = cv.take<float>(2 * 1024);
     m.st = cv.take<MindStats>(1);
@@ -756,14 +789,12 @@ static MindWs mind_layout(Carver& cv, int H, int W, int D, int ga, long long T) 
         m.blk = cv.take<unsigned>(3 * m.nblk);
         return m;
     }
-    if (T <= 0) return m;
+    if (pl.mean_threads == 0) return m;
     const size_t V = (size_t)H * W * D;
-    m.threads = (int)(T > 1024 ? 1024 : T);
-    m.two_pass = V >= 32768 && m.threads > 1;
     m.nt = 1; m.chunk = (long long)V;
-    if (m.two_pass) {
+    if (pl.two_pass) {
         m.nt = ((long long)V + 32767) / 32768;
-        if (m.nt > m.threads) m.nt = m.threads;
+        if (m.nt > pl.mean_threads) m.nt = pl.mean_threads;
         m.chunk = ((long long)V + m.nt - 1) / m.nt;
     }
     // level buffers: at most nv4 / 16, / 256, / 4096 rows of 32 floats per chunk
@@ -774,134 +805,95 @@ static MindWs mind_layout(Carver& cv, int H, int W, int D, int ga, long long T) 
     return m;
 }
 
-// min/max -> split grids -> stencil pass: raw patch SSDs in `raw` [12][V] (final channel order), statistics in *st
-static int mind_stencil(const float* img, int H, int W, int D, int radius, int dilation, float* raw, void* workspace,
-                        size_t workspace_bytes, MindStats** st_out, hipStream_t s, const MindRawLayout& lay = MindRawLayout{0, 0, 0, 0, 0}) {
-    Carver cv(workspace);
-    const long long T = options().mind_mean_threads;
-    const MindWs m = mind_layout(cv, H, W, D, 0, T);
-    MindStats* st = *st_out = m.st;
-    const size_t V = (size_t)H * W * D;
+// min/max partials -> statistics block with the split grids (every field of *st written)
+static void mind_stats_begin(const float* img, size_t V, const MindWs& m, hipStream_t s) {
     const int nb = (int)(V / 4096 + 1 < 1024 ? V / 4096 + 1 : 1024);
     hipLaunchKernelGGL(k_minmax_partial, dim3(nb), dim3(256), 0, s, img, V, m.part);
-    hipLaunchKernelGGL(k_mind_stats_init, dim3(1), dim3(256), 0, s, m.part, nb, (double)V, st);
+    hipLaunchKernelGGL(k_mind_stats_init, dim3(1), dim3(256), 0, s, m.part, nb, (double)V, m.st);
+}
+
+// min/max -> split grids -> stencil pass: raw patch SSDs in `raw` [12][V] (final channel order; blocked: plan.lay), statistics in *st
+static int mind_stencil(const MindPlan& pl, const float* img, float* raw, void* workspace, MindStats** st_out, hipStream_t s) {
+    Carver cv(workspace);
+    const MindWs m = mind_layout(cv, pl, 0);
+    MindStats* st = *st_out = m.st;
+    const size_t V = (size_t)pl.u.H * pl.u.W * pl.u.D;
+    mind_stats_begin(img, V, m, s);
     int rc;
-    switch (radius) {
-        case 1: rc = mind_launch_r<1>(img, H, W, D, dilation, st, raw, s, lay); break;
-        case 2: rc = mind_launch_r<2>(img, H, W, D, dilation, st, raw, s, lay); break;
-        default: rc = mind_launch_r<3>(img, H, W, D, dilation, st, raw, s, lay); break;
+    switch (pl.u.radius) {
+        case 1: rc = mind_launch_r<1>(pl, img, st, raw, s); break;
+        case 2: rc = mind_launch_r<2>(pl, img, st, raw, s); break;
+        default: rc = mind_launch_r<3>(pl, img, st, raw, s); break;
     }
-    if (rc || T <= 0) return rc;
+    if (rc || pl.mean_threads == 0) return rc;
     // reference-bits mode: torch's own mean instead of the exactly rounded one
     hipLaunchKernelGGL(k_mind_var, dim3((unsigned)cdiv64((int64_t)V, 256)), dim3(256), 0, s, raw, V, m.var);
-    if (m.two_pass) (void)hipMemsetAsync(m.slots, 0, 1024 * sizeof(float), s);              // unused slots keep the identity
+    if (pl.two_pass) (void)hipMemsetAsync(m.slots, 0, 1024 * sizeof(float), s);              // unused slots keep the identity
     auto blocks = [](long long nrows) { return (unsigned)((nrows * 32 + 255) / 256 > 0 ? (nrows * 32 + 255) / 256 : 1); };
     hipLaunchKernelGGL(k_torch_sum_level<0>, dim3(blocks(m.rows / 16 + 1), (unsigned)m.nt), dim3(256), 0, s, m.var, m.B0, (long long)V, m.chunk, 0ll, m.s0);
     hipLaunchKernelGGL(k_torch_sum_level<1>, dim3(blocks(m.rows / 256 + 1), (unsigned)m.nt), dim3(256), 0, s, m.B0, m.B1, (long long)V, m.chunk, m.s0, m.s1);
     hipLaunchKernelGGL(k_torch_sum_level<2>, dim3(blocks(m.rows / 4096 + 1), (unsigned)m.nt), dim3(256), 0, s, m.B1, m.B2, (long long)V, m.chunk, m.s1, m.s2);
     hipLaunchKernelGGL(k_torch_sum_chunks, dim3((unsigned)m.nt), dim3(64), 0, s, m.var, m.B0, m.B1, m.B2, (long long)V, m.chunk, m.s0, m.s1, m.s2, m.slots);
-    hipLaunchKernelGGL(k_torch_sum_final, dim3(1), dim3(1), 0, s, m.slots, m.threads, m.two_pass ? 1 : 0, (long long)V, st);
+    hipLaunchKernelGGL(k_torch_sum_final, dim3(1), dim3(1), 0, s, m.slots, pl.mean_threads, pl.two_pass ? 1 : 0, (long long)V, st);
     return check_last("mind_mean");
 }
 
-static int mind_check(const float* img, const float* out, const void* workspace, int H, int W, int D, int radius, int dilation,
-                      size_t workspace_bytes) {
+// the larger of the single-pass and the two-pass layout, whichever the plan runs (callers cache the size)
+static size_t mind_ws_bytes(const MindPlan& pl) {
+    Carver single, two;
+    mind_layout(single, pl, 2);                                    // the single pass with the smallest window has the most blocks
+    mind_layout(two, pl, 0);
+    return std::max(ws_query(single), ws_query(two));
+}
+
+static int mind_check(const MindPlan& pl, const float* img, const float* out, const void* workspace, size_t workspace_bytes) {
+    const MindUse& u = pl.u;
     CVX_REQUIRE(img && out && workspace, "cvx_mindssc_f32: null pointer");
-    CVX_REQUIRE(H > 0 && W > 0 && D > 0, "cvx_mindssc_f32: bad extent %dx%dx%d", H, W, D);
-    CVX_REQUIRE(radius >= 1 && radius <= 3, "cvx_mindssc_f32: radius %d not in 1..3", radius);
-    CVX_REQUIRE(dilation >= 1 && dilation <= 4, "cvx_mindssc_f32: dilation %d not in 1..4", dilation);
-    if (workspace_bytes < cvx_mindssc_workspace_bytes(H, W, D, radius, dilation))
-        return fail(CVX_ERR_WORKSPACE, "cvx_mindssc_f32: workspace too small");
-    if (mind_lds_bytes(radius, dilation, 1, 32) > 160 * 1024)
-        return fail(CVX_ERR_UNSUPPORTED, "cvx_mindssc_f32: radius %d dilation %d exceeds the LDS tile", radius, dilation);
+    CVX_REQUIRE(u.H > 0 && u.W > 0 && u.D > 0, "cvx_mindssc_f32: bad extent %dx%dx%d", u.H, u.W, u.D);
+    CVX_REQUIRE(u.radius >= 1 && u.radius <= 3, "cvx_mindssc_f32: radius %d not in 1..3", u.radius);
+    CVX_REQUIRE(u.dilation >= 1 && u.dilation <= 4, "cvx_mindssc_f32: dilation %d not in 1..4", u.dilation);
+    if (workspace_bytes < mind_ws_bytes(pl)) return fail(CVX_ERR_WORKSPACE, "cvx_mindssc_f32: workspace too small");
+    if (pl.stencil == MindStencil::Unsupported)
+        return fail(CVX_ERR_UNSUPPORTED, "cvx_mindssc_f32: radius %d dilation %d exceeds the LDS tile", u.radius, u.dilation);
     return CVX_OK;
 }
 
-// tile edge of the fused finish + pooling pass for window sizes (g1, g2), 0 if it does not apply
-static int mind_pool_tile(int H, int W, int D, int g1, int g2) {
-    const int T = g1 > g2 ? g1 : g2, g = g1 > g2 ? g2 : g1;
-    (void)H; (void)W;
-    if ((D & 1) != 0) return 0;                                       // 8-byte row segments
-    const bool ok = (T == 6 && (g == 2 || g == 3 || g == 6)) || (T == 4 && (g == 2 || g == 4)) || (T == 2 && g == 2);
-    return ok ? T : 0;                                                // 12 * T * T * 24 floats of LDS: 41 KB for T = 6
-}
-bool mind_pooled_supported(int H, int W, int D, int g1, int g2) { return mind_pool_tile(H, W, D, g1, g2 > 0 ? g2 : g1) != 0; }
-
-// MIND-SSC of `img` delivered only as avg_pool3d(., g1, stride g1) -> out1 and (g2 > 0) avg_pool3d(., g2, stride g2) -> out2;
-// `raw` is a 12*V float scratch (the raw patch SSDs).  Same values as cvx_mindssc_f32 followed by cvx_avgpool_f32.
-// The stencil pass of the pooled path writes its raw SSDs blocked by the second pass's tiles (MindRawLayout) when the marching kernel runs it,
-// the global mean is the exactly rounded one (the reference-bits mean walks the planar volume) and option mind_blocked is on.
-// mind_pooled_raw_floats: size of the `raw` scratch the caller must provide (the tiles overhang the volume).
-static bool mind_pooled_blocked(const float* img, const float* raw, int H, int W, int D, int radius, int dilation, int g1, int g2) {
-    return options().mind_blocked != 0 && options().mind_tiled == 0 && options().mind_mean_threads <= 0 && mind_pool_tile(H, W, D, g1, g2 > 0 ? g2 : g1) != 0 &&
-           mind_march_supported(img, raw, H, W, D, radius, dilation);
-}
-size_t mind_pooled_raw_floats(int H, int W, int D, int g1, int g2) {
-    const int T = mind_pool_tile(H, W, D, g1, g2 > 0 ? g2 : g1);
-    const size_t planar = (size_t)12 * H * W * D;
-    if (T == 0) return planar;
-    const size_t blocked = (size_t)cdiv(D, MP_TX) * cdiv(W, T) * cdiv(H, T) * 12 * T * T * MP_TX;
-    return blocked > planar ? blocked : planar;
-}
-// the single-pass kernel applies: the marching stencil's geometry, a window pair it is instantiated for, the library's own exp and the exactly
-// rounded mean (reference-bits mode walks the planar variance volume and corrects exp through a table)
-static bool mind_single_pass(const float* img, int H, int W, int D, int radius, int dilation, int ga, int gb) {
-    return options().mind_single != 0 && options().mind_tiled == 0 && options().mind_mean_threads <= 0 && mind_exp_table().tbl == nullptr &&
-           mind_single_supported(ga, gb) && mind_march_supported(img, img, H, W, D, radius, dilation);
-}
-// records (with out2): out2 receives the g2-pooled descriptor as feature records instead of planar channels (needs g2 <= g1); see
-// mind_pooled_records_supported
-bool mind_pooled_records_supported(int H, int W, int D, int g1, int g2) { return g2 > 0 && g2 <= g1 && mind_pool_tile(H, W, D, g1, g2) != 0; }
-int launch_mind_pooled(const float* img, int H, int W, int D, int radius, int dilation, int g1, float* out1, int g2, float* out2,
-                       float* raw, void* workspace, size_t workspace_bytes, hipStream_t s, int records) {
-    int rc = mind_check(img, raw, workspace, H, W, D, radius, dilation, workspace_bytes);
+// MIND-SSC of `img` delivered only as avg_pool3d(., g1, stride g1) -> out1 and (g2 > 0) avg_pool3d(., g2, stride g2) -> out2, or (plan.records) out2 as
+// the g2-pooled feature records.  Same values as cvx_mindssc_f32 followed by cvx_avgpool_f32.  `raw`: the two-pass scratch of plan.raw_floats floats.
+int launch_mind_pooled(const MindPlan& pl, const float* img, float* out1, float* out2, float* raw, void* workspace, size_t workspace_bytes, hipStream_t s,
+                       MindStats** st_out) {
+    const MindUse& u = pl.u;
+    int rc = mind_check(pl, img, pl.single ? img : raw, workspace, workspace_bytes);         // (the single pass does not touch `raw`)
     if (rc) return rc;
-    const int T = mind_pool_tile(H, W, D, g1, g2 > 0 ? g2 : g1);
-    if (T == 0 || !out1) return fail(CVX_ERR_UNSUPPORTED, "mind_pooled: window sizes %d, %d do not tile", g1, g2);
+    if (pl.T == 0 || !out1) return fail(CVX_ERR_UNSUPPORTED, "mind_pooled: window sizes %d, %d do not tile", u.g1, u.g2);
+    if (pl.records && !out2) return fail(CVX_ERR_UNSUPPORTED, "mind_pooled: feature records need 0 < g2 <= g1");
+    float* oa = pl.swap ? out2 : out1;
+    float* ob = u.g2 > 0 && !pl.records ? (pl.swap ? out1 : out2) : nullptr;
+    void* rec = pl.records ? out2 : nullptr;             // records: 1 = float32, 2 = half precision
+    const int rec_half = pl.records == 2 ? 1 : 0;
     MindStats* st = nullptr;
-    // (ga, gb) = (larger, smaller) window; the larger one goes to the matching output
-    const bool swap = g2 > g1;
-    const int ga = swap ? g2 : g1, gb = g2 > 0 ? (swap ? g1 : g2) : g1;
-    float* oa = swap ? out2 : out1;
-    float* ob = g2 > 0 ? (swap ? out1 : out2) : nullptr;
-    if (records && (swap || !out2)) return fail(CVX_ERR_UNSUPPORTED, "mind_pooled: feature records need 0 < g2 <= g1");
-    void* rec = records ? out2 : nullptr;             // records: 1 = float32, 2 = half precision
-    if (records) ob = nullptr;
-    if (mind_single_pass(img, H, W, D, radius, dilation, ga, gb)) {
+    if (pl.single) {
         // ONE pass over the image (mindmarch.hip::k_mind_march_pool) + the repair of the blocks where the variance clamp binds; `raw` is not touched
         Carver cv(workspace);
-        const MindWs m = mind_layout(cv, H, W, D, ga, 0);
+        const MindWs m = mind_layout(cv, pl, pl.ga);
         st = m.st;
-        const size_t V = (size_t)H * W * D;
-        const int nb = (int)(V / 4096 + 1 < 1024 ? V / 4096 + 1 : 1024);
-        hipLaunchKernelGGL(k_minmax_partial, dim3(nb), dim3(256), 0, s, img, V, m.part);
-        hipLaunchKernelGGL(k_mind_stats_init, dim3(1), dim3(256), 0, s, m.part, nb, (double)V, st);
-        launch_mind_march_pool(img, H, W, D, ga, oa, gb, records ? rec : static_cast<void*>(ob), records, st, m.blk, s);
+        mind_stats_begin(img, (size_t)u.H * u.W * u.D, m, s);
+        launch_mind_march_pool(pl, img, oa, pl.records ? rec : static_cast<void*>(ob), st, m.blk, s);
         const unsigned rgrid = (unsigned)(m.nblk / 64 + 1 < 1024 ? m.nblk / 64 + 1 : 1024);
-        const int force = options().mind_single == 2 ? 1 : 0;           // 2: every block through the repair kernel (test of the exact recomputation)
-#define CVX_MR(GA, GB) hipLaunchKernelGGL((k_mind_repair<GA, GB>), dim3(rgrid), dim3(MR_NT), 0, s, img, H, W, D, st, m.blk, oa, ob, rec, records == 2 ? 1 : 0, mind_exp_table(), force)
-        if (ga == 6 && gb == 2) CVX_MR(6, 2);
-        else if (ga == 6 && gb == 3) CVX_MR(6, 3);
-        else if (ga == 6 && gb == 6) CVX_MR(6, 6);
-        else if (ga == 4 && gb == 2) CVX_MR(4, 2);
-        else if (ga == 4 && gb == 4) CVX_MR(4, 4);
-        else CVX_MR(2, 2);
-#undef CVX_MR
-        return check_last("mind_march_pool");
+        mind_pair_dispatch(pl.ga, pl.gb, [&](auto ga, auto gb) {
+            hipLaunchKernelGGL((k_mind_repair<decltype(ga)::value, decltype(gb)::value>), dim3(rgrid), dim3(MR_NT), 0, s, img, u.H, u.W, u.D, st, m.blk, oa, ob, rec,
+                               rec_half, mind_exp_table(), pl.force_repair ? 1 : 0);
+        });
+    } else {
+        if ((rc = mind_stencil(pl, img, raw, workspace, &st, s))) return rc;
+        const dim3 grid(cdiv(u.D, MP_TX), cdiv(u.W, pl.T), cdiv(u.H, pl.T));
+        mind_pair_dispatch(pl.ga, pl.gb, [&](auto ga, auto gb) {
+            hipLaunchKernelGGL((k_mind_finish_pool<decltype(ga)::value, decltype(gb)::value>), grid, dim3(MP_NT), 0, s, raw, u.H, u.W, u.D, st, oa, ob, rec, rec_half,
+                               mind_exp_table(), pl.lay);
+        });
     }
-    const dim3 grid(cdiv(D, MP_TX), cdiv(W, T), cdiv(H, T));
-    const MindRawLayout lay = mind_pooled_blocked(img, raw, H, W, D, radius, dilation, g1, g2)
-                                  ? MindRawLayout{T, (int)grid.x, (int)grid.y, (size_t)12 * T * T * MP_TX, (size_t)T * T * MP_TX} : MindRawLayout{0, 0, 0, 0, 0};
-    if ((rc = mind_stencil(img, H, W, D, radius, dilation, raw, workspace, workspace_bytes, &st, s, lay))) return rc;
-#define CVX_MP(GA, GB) hipLaunchKernelGGL((k_mind_finish_pool<GA, GB>), grid, dim3(MP_NT), 0, s, raw, H, W, D, st, oa, ob, rec, records == 2 ? 1 : 0, mind_exp_table(), lay)
-    if (ga == 6 && gb == 2) CVX_MP(6, 2);
-    else if (ga == 6 && gb == 3) CVX_MP(6, 3);
-    else if (ga == 6 && gb == 6) CVX_MP(6, 6);
-    else if (ga == 4 && gb == 2) CVX_MP(4, 2);
-    else if (ga == 4 && gb == 4) CVX_MP(4, 4);
-    else CVX_MP(2, 2);
-#undef CVX_MP
-    return check_last("mind_finish_pool");
+    if (st_out) *st_out = st;
+    return check_last(pl.single ? "mind_march_pool" : "mind_finish_pool");
 }
 
 }  // namespace cvx
@@ -909,20 +901,14 @@ int launch_mind_pooled(const float* img, int H, int W, int D, int radius, int di
 using namespace cvx;
 
 extern "C" size_t cvx_mindssc_workspace_bytes(int H, int W, int D, int radius, int dilation) {
-    (void)radius; (void)dilation;
-    Carver single, two;
-    mind_layout(single, H, W, D, 2, 0);                            // the single pass with the smallest window has the most blocks
-    mind_layout(two, H, W, D, 0, options().mind_mean_threads);
-    return std::max(ws_query(single), ws_query(two));
+    return mind_ws_bytes(mind_plan(MindUse{H, W, D, radius, dilation, 0, 0, 0, true, true}));
 }
 
+// (alignment is the caller's: the query assumes a 16-byte aligned image; see the header for the image that is not)
 extern "C" size_t cvx_mindssc_pooled_scratch_bytes(int H, int W, int D, int radius, int dilation, int g1, int g2) {
     if (H <= 0 || W <= 0 || D <= 0) return 0;
-    const bool swap = g2 > g1;
-    const int ga = swap ? g2 : g1, gb = g2 > 0 ? (swap ? g1 : g2) : g1;
-    // (alignment is the caller's hipMalloc: the predicate is asked with an aligned pointer)
-    if (mind_single_pass(reinterpret_cast<const float*>(uintptr_t(256)), H, W, D, radius, dilation, ga, gb)) return 0;
-    return mind_pooled_raw_floats(H, W, D, g1, g2) * sizeof(float);
+    const MindPlan pl = mind_plan(MindUse{H, W, D, radius, dilation, g1, g2, 0, true, true});
+    return pl.single ? 0 : pl.raw_floats * sizeof(float);
 }
 
 extern "C" int cvx_mindssc_pooled_f32(const float* img, int H, int W, int D, int radius, int dilation, int g1, float* out1, int g2, float* out2,
@@ -931,22 +917,18 @@ extern "C" int cvx_mindssc_pooled_f32(const float* img, int H, int W, int D, int
     CVX_REQUIRE(H > 0 && W > 0 && D > 0, "cvx_mindssc_pooled_f32: bad extent %dx%dx%d", H, W, D);
     CVX_REQUIRE(g1 >= 1 && g2 >= 0, "cvx_mindssc_pooled_f32: bad windows %d, %d", g1, g2);
     CVX_REQUIRE(g2 == 0 || out2, "cvx_mindssc_pooled_f32: second output missing");
-    if (!mind_pooled_supported(H, W, D, g1, g2)) return fail(CVX_ERR_UNSUPPORTED, "cvx_mindssc_pooled_f32: windows %d, %d do not tile", g1, g2);
-    const size_t need = cvx_mindssc_pooled_scratch_bytes(H, W, D, radius, dilation, g1, g2);
-    const bool single = need == 0 && (reinterpret_cast<uintptr_t>(img) & 15) == 0;
-    if (!single) {
-        const size_t two = mind_pooled_raw_floats(H, W, D, g1, g2) * sizeof(float);
-        if (!scratch || scratch_bytes < two) return fail(CVX_ERR_WORKSPACE, "cvx_mindssc_pooled_f32: scratch %zu < %zu bytes", scratch_bytes, two);
-    }
+    const MindPlan pl = mind_plan(MindUse{H, W, D, radius, dilation, g1, g2, 0, aligned16(img), aligned16(scratch)});
+    if (pl.T == 0) return fail(CVX_ERR_UNSUPPORTED, "cvx_mindssc_pooled_f32: windows %d, %d do not tile", g1, g2);
+    const size_t two = pl.raw_floats * sizeof(float);
+    if (!pl.single && (!scratch || scratch_bytes < two))
+        return fail(CVX_ERR_WORKSPACE, "cvx_mindssc_pooled_f32: scratch %zu < %zu bytes%s", scratch_bytes, two,
+                    pl.single_unaligned ? " (the image is not 16-byte aligned: the single pass does not apply, two passes need the scratch)" : "");
     hipStream_t s = as_stream(stream);
-    // (launch_mind_pooled validates through `raw`: the image itself stands in when the single pass needs no scratch)
-    int rc = launch_mind_pooled(img, H, W, D, radius, dilation, g1, out1, g2, g2 > 0 ? out2 : nullptr, single ? const_cast<float*>(img) : static_cast<float*>(scratch),
-                                workspace, workspace_bytes, s, 0);
+    MindStats* st = nullptr;
+    const int rc = launch_mind_pooled(pl, img, out1, g2 > 0 ? out2 : nullptr, static_cast<float*>(scratch), workspace, workspace_bytes, s, &st);
     if (rc || !repaired_host) return rc;
     *repaired_host = 0;
-    if (single) {
-        Carver cv(workspace);
-        const MindStats* st = mind_layout(cv, H, W, D, 0, 0).st;
+    if (pl.single) {
         unsigned n = 0;
         if (hipMemcpyAsync(&n, &st->n_repair, sizeof(n), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
             return check_last("cvx_mindssc_pooled_f32: repair count");
@@ -957,13 +939,14 @@ extern "C" int cvx_mindssc_pooled_f32(const float* img, int H, int W, int D, int
 
 extern "C" int cvx_mindssc_f32(const float* img, int H, int W, int D, int radius, int dilation, float* out,
                                void* workspace, size_t workspace_bytes, void* stream) {
-    int rc = mind_check(img, out, workspace, H, W, D, radius, dilation, workspace_bytes);
+    const MindPlan pl = mind_plan(MindUse{H, W, D, radius, dilation, 0, 0, 0, aligned16(img), aligned16(out)});
+    int rc = mind_check(pl, img, out, workspace, workspace_bytes);
     if (rc) return rc;
     hipStream_t s = as_stream(stream);
     MindStats* st = nullptr;
-    if ((rc = mind_stencil(img, H, W, D, radius, dilation, out, workspace, workspace_bytes, &st, s))) return rc;
+    if ((rc = mind_stencil(pl, img, out, workspace, &st, s))) return rc;
     const size_t V = (size_t)H * W * D;
-    if (V % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0)
+    if (pl.finish4)
         hipLaunchKernelGGL(k_mind_finish<4>, dim3((unsigned)cdiv64((int64_t)(V / 4), 256)), dim3(256), 0, s, out, V, st, mind_exp_table());
     else
         hipLaunchKernelGGL(k_mind_finish<1>, dim3((unsigned)cdiv64((int64_t)V, 256)), dim3(256), 0, s, out, V, st, mind_exp_table());

@@ -570,27 +570,13 @@ static void launch_ms(const MSArgs& a0, hipStream_t s) {
     hipLaunchKernelGGL((k_mind_march_pool<GA, GB, REC>), dim3(grid), dim3(MM_NT), 0, s, a);
 }
 
-bool mind_single_supported(int ga, int gb) {
-    return (ga == 6 && (gb == 2 || gb == 3 || gb == 6)) || (ga == 4 && (gb == 2 || gb == 4)) || (ga == 2 && gb == 2);
-}
-// ga >= gb, gb divides ga (mind_single_supported); out2 null: single pooling; records: out2 receives feature records (1 float32, 2 half precision)
-void launch_mind_march_pool(const float* img, int H, int W, int D, int ga, float* out1, int gb, void* out2, int records, MindStats* st, unsigned* blk, hipStream_t s) {
-    MSArgs a = {img, out1, out2, st, blk, H, W, D, 0, 0, 0, 0, records == 2 ? 1 : 0, cdiv(W, ga), cdiv(D, ga)};
-    const bool rec = records != 0;
-#define CVX_MS(GA, GB) do { if (rec) launch_ms<GA, GB, true>(a, s); else launch_ms<GA, GB, false>(a, s); } while (0)
-    if (ga == 6 && gb == 2) CVX_MS(6, 2);
-    else if (ga == 6 && gb == 3) CVX_MS(6, 3);
-    else if (ga == 6 && gb == 6) CVX_MS(6, 6);
-    else if (ga == 4 && gb == 2) CVX_MS(4, 2);
-    else if (ga == 4 && gb == 4) CVX_MS(4, 4);
-    else CVX_MS(2, 2);
-#undef CVX_MS
-}
-
-bool mind_march_supported(const float* img, const float* out, int H, int W, int D, int radius, int dilation) {
-    auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    (void)H; (void)W;
-    return radius == 1 && dilation == 2 && (D & 3) == 0 && al(img) && al(out);
+void launch_mind_march_pool(const MindPlan& pl, const float* img, float* out1, void* out2, MindStats* st, unsigned* blk, hipStream_t s) {
+    const MindUse& u = pl.u;
+    const MSArgs a = {img, out1, out2, st, blk, u.H, u.W, u.D, 0, 0, 0, 0, pl.records == 2 ? 1 : 0, cdiv(u.W, pl.ga), cdiv(u.D, pl.ga)};
+    mind_pair_dispatch(pl.ga, pl.gb, [&](auto ga, auto gb) {
+        if (pl.records) launch_ms<decltype(ga)::value, decltype(gb)::value, true>(a, s);
+        else launch_ms<decltype(ga)::value, decltype(gb)::value, false>(a, s);
+    });
 }
 
 template <typename G>
@@ -608,12 +594,9 @@ static void launch_mind_march_g(const float* img, int H, int W, int D, MindStats
     hipLaunchKernelGGL(k_mind_march<G>, dim3(grid), dim3(MM_NT), 0, s, img, H, W, D, zc_len, nzc, nyt, nxt, st, out, lay);
 }
 
-void launch_mind_march(const float* img, int H, int W, int D, MindStats* st, float* out, hipStream_t s, MindRawLayout lay) {
-    const int force = (int)options().mm_tx;
-    const int rem = D % 64;
-    const bool narrow = force ? force == 32 : (rem != 0 && rem <= 32);
-    if (narrow) launch_mind_march_g<MMGeo<16, 32>>(img, H, W, D, st, out, s, lay);
-    else launch_mind_march_g<MMGeo<8, 64>>(img, H, W, D, st, out, s, lay);
+void launch_mind_march(const MindPlan& pl, const float* img, MindStats* st, float* out, hipStream_t s) {
+    if (pl.stencil == MindStencil::March16x32) launch_mind_march_g<MMGeo<16, 32>>(img, pl.u.H, pl.u.W, pl.u.D, st, out, s, pl.lay);
+    else launch_mind_march_g<MMGeo<8, 64>>(img, pl.u.H, pl.u.W, pl.u.D, st, out, s, pl.lay);
 }
 
 }  // namespace cvx

@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "cvx_common.h"
+#include "mind_common.h"
 
 namespace cvx {
 
@@ -113,8 +114,8 @@ static PairLayout pair_layout(const cvx_pair_params& p, int n_snap = 0, int max_
     Carver cv; cv.take_bytes(1);    // offset 0 is reserved as "unused"
     const size_t f = sizeof(float);
     if (p.n_feat == 0) {
-        // (the pooled path's raw patch SSDs may be blocked by tiles that overhang the volume: mind_pooled_raw_floats >= 12 V)
-        const size_t raw_floats = mind_pooled_raw_floats(p.H, p.W, p.D, p.grid_sp, p.lambda_weight > 0 ? p.grid_sp_adam : 0);
+        // (the pooled path's raw patch SSDs may be blocked by tiles that overhang the volume: MindPlan::raw_floats >= 12 V)
+        const size_t raw_floats = mind_plan(MindUse{p.H, p.W, p.D, p.mind_r, p.mind_d, p.grid_sp, p.lambda_weight > 0 ? p.grid_sp_adam : 0, 0, true, true}).raw_floats;
         L.featF = cv.take_bytes(f * raw_floats);
         L.featM = cv.take_bytes(f * raw_floats);
         L.mind_ws = cv.take_bytes(cvx_mindssc_workspace_bytes(p.H, p.W, p.D, p.mind_r, p.mind_d));
@@ -338,14 +339,16 @@ struct PairRun {
         // MIND path: the descriptor is consumed only through its two stride poolings, so when the window sizes tile it is never
         // written at full resolution (launch_mind_pooled: raw patch SSDs -> normalise + exp + both poolings in one pass)
         const bool adam = p->lambda_weight > 0;
-        pooled_mind = p->n_feat == 0 && mind_pooled_supported(p->H, p->W, p->D, p->grid_sp, adam ? p->grid_sp_adam : 0);
-        // the Adam-grid pooling of the descriptor written as the loop's feature records (no planar copy, no re-packing pass)
-        mind_records = pooled_mind && adam && options().mind_records != 0 && mind_pooled_records_supported(p->H, p->W, p->D, p->grid_sp, p->grid_sp_adam);
-        const int rec_kind = mind_records ? (p->fp16_storage ? 2 : 1) : 0;
+        // the Adam-grid pooling of the descriptor written as the loop's feature records (no planar copy, no re-packing pass) where the plan allows
+        const int g2 = adam ? p->grid_sp_adam : 0, want_records = adam && options().mind_records != 0 ? (p->fp16_storage ? 2 : 1) : 0;
         if (p->n_feat == 0) {
+            auto plan_of = [&](const float* img, const float* raw) {
+                return mind_plan(MindUse{p->H, p->W, p->D, p->mind_r, p->mind_d, p->grid_sp, g2, want_records, aligned16(img), aligned16(raw)});
+            };
+            const MindPlan plF = plan_of(img_fixed, F(L.featF)), plM = plan_of(img_moving, F(L.featM));
+            pooled_mind = plF.T != 0; mind_records = plF.records != 0;
             const size_t mws = cvx_mindssc_workspace_bytes(p->H, p->W, p->D, p->mind_r, p->mind_d);
             if (pooled_mind) {
-                const int g2 = adam ? p->grid_sp_adam : 0;
                 // The two images are independent until `correlate`.  Option mind_overlap = 1 runs the moving image's pass on a side stream (one
                 // image's VALU-bound stencil beside the other's memory-bound normalise + pool pass); measured on the benchmark pair: 0.52 vs
                 // 0.53 ms for the stage and a SLOWER pair (7.92 vs 7.76 ms) -- every one of these kernels fills the chip on its own -- so the
@@ -354,10 +357,8 @@ struct PairRun {
                 const bool overlap = options().mind_overlap != 0 && side_stream(&side, &ev_fork, &ev_join);
                 if (overlap) { (void)hipEventRecord(ev_fork, s); (void)hipStreamWaitEvent(side, ev_fork, 0); }
                 else side = s;
-                if ((rc = launch_mind_pooled(img_fixed, p->H, p->W, p->D, p->mind_r, p->mind_d, p->grid_sp, F(L.fs), g2, adam ? F(L.F2) : nullptr,
-                                             F(L.featF), ws + L.mind_ws, mws, s, rec_kind))) return rc;
-                rc = launch_mind_pooled(img_moving, p->H, p->W, p->D, p->mind_r, p->mind_d, p->grid_sp, F(L.ms), g2, adam ? F(L.M2) : nullptr,
-                                        F(L.featM), ws + (overlap ? L.mind_ws2 : L.mind_ws), mws, side, rec_kind);
+                if ((rc = launch_mind_pooled(plF, img_fixed, F(L.fs), adam ? F(L.F2) : nullptr, F(L.featF), ws + L.mind_ws, mws, s))) return rc;
+                rc = launch_mind_pooled(plM, img_moving, F(L.ms), adam ? F(L.M2) : nullptr, F(L.featM), ws + (overlap ? L.mind_ws2 : L.mind_ws), mws, side);
                 if (overlap) { (void)hipEventRecord(ev_join, side); (void)hipStreamWaitEvent(s, ev_join, 0); }      // (joined even after an error)
                 if (rc) return rc;
             } else {
@@ -368,7 +369,6 @@ struct PairRun {
         }
         if (labels) {
             // label path: the weighted one-hot volumes are consumed only through the same two poolings and are never written either
-            const int g2 = adam ? p->grid_sp_adam : 0;
             if ((rc = launch_label_pooled(labels->fixed, p->H, p->W, p->D, L.C, labels->present, labels->weights, labels->mult, p->grid_sp, F(L.fs), g2,
                                           adam ? F(L.F2) : nullptr, s))) return rc;
             if ((rc = launch_label_pooled(labels->moving, p->H, p->W, p->D, L.C, labels->present, labels->weights, labels->mult, p->grid_sp, F(L.ms), g2,

@@ -142,10 +142,14 @@ int cvx_mindssc_f32(const float* img, int H, int W, int D, int radius, int dilat
  *   unclamped variance inside the stencil kernel, the pooled cells of the few blocks where the variance clamp of :60-62 binds recomputed once
  *   the global mean is known); other settings take two passes through `scratch` (cvx_mindssc_pooled_scratch_bytes, may be 0 bytes / NULL
  *   ONLY when that function returns 0).  CVX_ERR_UNSUPPORTED when the windows do not tile (use the two separate operators).
- *   workspace: cvx_mindssc_workspace_bytes.  repaired_host (nullable): receives the number of recomputed blocks (synchronises the stream). */
-size_t cvx_mindssc_pooled_scratch_bytes(int H, int W, int D, int radius, int dilation, int g1, int g2);
+ *   workspace: cvx_mindssc_workspace_bytes.  repaired_host (nullable): receives the number of recomputed blocks (synchronises the stream).
+ *   ALIGNMENT: cvx_mindssc_pooled_scratch_bytes ASSUMES `img` is 16-byte aligned (it does not see the pointer).  The single pass needs that
+ *   alignment; an image that is not 16-byte aligned always takes the two passes and needs their scratch whatever the query said -- the size the
+ *   query returns with option mind_single = 0: 4 bytes x 12 channels x max(H W D, the volume rounded up to whole g x g x 24 tiles, g = the larger
+ *   window).  Without it cvx_mindssc_pooled_f32 answers CVX_ERR_WORKSPACE and says so; nothing is written. */
+size_t cvx_mindssc_pooled_scratch_bytes(int H, int W, int D, int radius, int dilation, int g1, int g2);   /* assumes a 16-byte aligned img, see above */
 int cvx_mindssc_pooled_f32(const float* img, int H, int W, int D, int radius, int dilation, int g1, float* out1, int g2, float* out2,
-                           void* scratch, size_t scratch_bytes, void* workspace, size_t workspace_bytes, int* repaired_host, void* stream);
+                           void* scratch, size_t scratch_bytes, void* workspace, size_t workspace_bytes, int* repaired_host, void* stream);   /* img not 16-byte aligned: two-pass scratch required, see above */
 
 /* F.avg_pool3d(x, g, stride=g)                              convex_adam_MIND.py:118-119,149-150
  *   in [C][H][W][D] -> out [C][H/g][W/g][D/g] (floor) */

@@ -43,6 +43,31 @@ def test_library_exports_every_declared_symbol(L):
     assert sorted(_lib.SIGNATURES) == header_functions()
 
 
+def test_pooled_descriptor_states_its_alignment_contract(L):
+    """cvx_mindssc_pooled_scratch_bytes assumes a 16-byte aligned image (include/convexadam_hip.h).  With the single pass on it names no scratch;
+    an image that is not 16-byte aligned takes two passes and is refused without their scratch -- CVX_ERR_WORKSPACE, and the message says why.
+    The aligned image gets past the scratch check (and is refused for its empty workspace here: nothing is launched)."""
+    H, W, D, r, d, g1, g2 = 7, 6, 8, 1, 2, 6, 2
+    out, ws = C.c_void_p(4096), C.c_void_p(8192)
+    old = L.cvx_get_option(b"mind_single")
+    try:
+        assert L.cvx_set_option(b"mind_single", 0) == 0
+        # two passes: 12 channels of raw distances, planar (12 V floats) or blocked by the second pass's 6 x 6 x 24 tiles, whichever is larger --
+        # at 7 x 6 x 8 the 2 x 1 x 1 tiles overhang the volume (12 * 2 * 6 * 6 * 24 floats against 12 * 7 * 6 * 8)
+        two_pass = 4 * max(12 * 7 * 6 * 8, 12 * (2 * 1 * 1) * (6 * 6 * 24))
+        assert L.cvx_mindssc_pooled_scratch_bytes(H, W, D, r, d, g1, g2) == two_pass == 82944
+        assert L.cvx_set_option(b"mind_single", 1) == 0
+        assert L.cvx_mindssc_pooled_scratch_bytes(H, W, D, r, d, g1, g2) == 0
+        rc = L.cvx_mindssc_pooled_f32(C.c_void_p(256 + 4), H, W, D, r, d, g1, out, g2, out, None, 0, ws, 1 << 30, None, None)
+        msg = L.cvx_last_error()
+        assert rc == -2 and b"scratch" in msg and b"16-byte" in msg, (rc, msg)
+        rc = L.cvx_mindssc_pooled_f32(C.c_void_p(256), H, W, D, r, d, g1, out, g2, out, None, 0, ws, 0, None, None)
+        msg = L.cvx_last_error()
+        assert rc == -2 and b"workspace" in msg and b"scratch" not in msg, (rc, msg)
+    finally:
+        L.cvx_set_option(b"mind_single", old)
+
+
 def test_pair_params_layout_matches_the_header_and_the_version_is_checked(L):
     """cvx_pair_params grew twice (ctx in round 3, adam_fast + reserved in round 4): the ctypes mirror must have the header's fields in
     the header's order, the library must report the header's CVX_ABI_VERSION, and the reserved tail must be refused when non-zero

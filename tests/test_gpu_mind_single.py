@@ -198,3 +198,110 @@ def test_pipeline_fields_identical_with_and_without_the_single_pass(single):
             single(v)
             outs.append(convex_adam_pt(fix, mov, dtype=torch.float16 if half else torch.float32, device=torch.device(DEV), **kw))
         assert np.array_equal(outs[0], outs[1]) and np.array_equal(outs[0], outs[2])
+
+
+# ---- the alignment contract of the two descriptor operators (include/convexadam_hip.h) --------------------------------------
+def one_float_in(x):
+    """the values of x as a view one float into a larger allocation: 4-byte aligned, not 16-byte aligned"""
+    buf = torch.empty(x.numel() + 8, dtype=torch.float32, device=DEV)
+    view = buf[1:1 + x.numel()]
+    view.copy_(x.reshape(-1))
+    assert view.data_ptr() % 16 == 4
+    return view
+
+
+def pooled_abi(img_dev, shape, g1, g2, scratch_bytes):
+    """cvx_mindssc_pooled_f32 on a device buffer as it is (no clone); outputs pre-filled with 0xA5 bytes -> rc, out1 bytes, out2 bytes, repairs"""
+    import ctypes as C
+    from convexadam_amd import _lib
+    L, (H, W, D) = _lib.lib(), shape
+    o1 = torch.full((12 * (H // g1) * (W // g1) * (D // g1) * 4,), 0xA5, dtype=torch.uint8, device=DEV)
+    o2 = torch.full((12 * (H // g2) * (W // g2) * (D // g2) * 4,), 0xA5, dtype=torch.uint8, device=DEV)
+    sc = torch.empty(max(scratch_bytes, 16), dtype=torch.uint8, device=DEV)
+    nws = L.cvx_mindssc_workspace_bytes(H, W, D, 1, 2)
+    ws = torch.empty(nws, dtype=torch.uint8, device=DEV)
+    rep = C.c_int(-1)
+    rc = L.cvx_mindssc_pooled_f32(_lib.ptr(img_dev), H, W, D, 1, 2, g1, _lib.ptr(o1), g2, _lib.ptr(o2), _lib.ptr(sc) if scratch_bytes else None, scratch_bytes,
+                                  _lib.ptr(ws), nws, C.byref(rep), _lib.stream_ptr(torch.device(DEV)))
+    torch.cuda.synchronize()
+    return rc, host(o1), host(o2), rep.value
+
+
+ALIGN_SHAPES = [(7, 6, 8), (13, 19, 92)]
+ALIGN_WINDOWS = [(6, 2), (4, 2)]
+
+
+@pytest.fixture(scope="module")
+def align_refs(orc):
+    """image and the oracle's two poolings as bytes, once per (shape, windows)"""
+    refs = {}
+    for shape in ALIGN_SHAPES:
+        img = textured(shape, 17 + shape[2])
+        m = orc.mindssc(img, 1, 2)
+        for g1, g2 in ALIGN_WINDOWS:
+            refs[shape, g1, g2] = img, orc.avgpool_stride(m, g1).astype(np.float32).tobytes(), orc.avgpool_stride(m, g2).astype(np.float32).tobytes()
+    return refs
+
+
+@pytest.mark.parametrize("v", [0, 1])
+@pytest.mark.parametrize("g1,g2", ALIGN_WINDOWS)
+@pytest.mark.parametrize("shape", ALIGN_SHAPES)
+def test_unaligned_image_takes_two_passes_through_the_scratch(align_refs, single, shape, g1, g2, v):
+    """An image that is not 16-byte aligned, with the two-pass scratch: the call succeeds whatever mind_single says, fell back to two passes
+    (no block repaired), and both poolings are byte-equal to the call on an aligned copy and to the oracle."""
+    from convexadam_amd._lib import lib
+    img, r1, r2 = align_refs[shape, g1, g2]
+    single(0)
+    two = lib().cvx_mindssc_pooled_scratch_bytes(*shape, 1, 2, g1, g2)
+    assert two >= 12 * shape[0] * shape[1] * shape[2] * 4
+    single(v)
+    x = dev(img)
+    assert x.data_ptr() % 16 == 0
+    rc_a, a1, a2, _ = pooled_abi(x, shape, g1, g2, two)
+    rc_u, u1, u2, rep = pooled_abi(one_float_in(x), shape, g1, g2, two)
+    assert rc_a == 0 and rc_u == 0
+    assert rep == 0
+    assert u1.tobytes() == a1.tobytes() == r1 and u2.tobytes() == a2.tobytes() == r2
+
+
+@pytest.mark.parametrize("g1,g2", ALIGN_WINDOWS)
+@pytest.mark.parametrize("shape", ALIGN_SHAPES)
+def test_unaligned_image_without_scratch_is_refused_untouched(align_refs, single, shape, g1, g2):
+    """mind_single = 1: the query (which assumes an aligned image) names no scratch; the unaligned image then takes two passes, which need it:
+    CVX_ERR_WORKSPACE, the message says why, nothing is written."""
+    from convexadam_amd._lib import lib
+    img = align_refs[shape, g1, g2][0]
+    single(1)
+    assert lib().cvx_mindssc_pooled_scratch_bytes(*shape, 1, 2, g1, g2) == 0
+    rc, o1, o2, _ = pooled_abi(one_float_in(dev(img)), shape, g1, g2, 0)
+    assert rc == -2 and b"scratch" in lib().cvx_last_error() and b"16-byte" in lib().cvx_last_error()
+    assert (o1 == 0xA5).all() and (o2 == 0xA5).all()
+
+
+def test_full_descriptor_with_unaligned_image_or_output(orc):
+    """cvx_mindssc_f32 at radius 1, dilation 2 with an image, then an output, that is not 16-byte aligned: the marching stencil does not apply and
+    k_mind runs (unaligned output: the scalar finish pass too) -- byte-equal to the aligned call and to the oracle."""
+    from convexadam_amd import _lib
+    L, shape = _lib.lib(), (3, 9, 8)
+    H, W, D = shape
+    V = H * W * D
+    img = textured(shape, 23)
+    ref = orc.mindssc(img, 1, 2).astype(np.float32).tobytes()
+    nws = L.cvx_mindssc_workspace_bytes(H, W, D, 1, 2)
+    ws = torch.empty(nws, dtype=torch.uint8, device=DEV)
+    x = dev(img)
+
+    def call(xin, out_offset):
+        buf = torch.full((12 * V + 8,), float("nan"), dtype=torch.float32, device=DEV)
+        out = buf[out_offset:out_offset + 12 * V]
+        assert out.data_ptr() % 16 == 4 * out_offset
+        rc = L.cvx_mindssc_f32(_lib.ptr(xin), H, W, D, 1, 2, _lib.ptr(out), _lib.ptr(ws), nws, _lib.stream_ptr(torch.device(DEV)))
+        torch.cuda.synchronize()
+        assert rc == 0, L.cvx_last_error()
+        assert torch.isnan(buf[:out_offset]).all() and torch.isnan(buf[out_offset + 12 * V:]).all()       # nothing written around the output
+        return host(out).tobytes()
+
+    aligned = call(x, 0)
+    assert aligned == ref
+    assert call(one_float_in(x), 0) == ref
+    assert call(x, 1) == ref

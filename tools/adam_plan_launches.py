@@ -81,12 +81,13 @@ def run_case(name):
     assert rc == 0, L.cvx_last_error()
 
 
-def collect(out_path, names, limit_s=180):
+def collect(out_path, names, limit_s=180, cases=None, script=__file__):
+    """cases / script: another tool's case table and file (tools/mind_plan_launches.py), run as `script --case NAME`"""
     res = {}
-    for name in names or CASES:
+    for name in names or cases or CASES:
         with tempfile.TemporaryDirectory() as tmp:
             cmd = ["timeout", "-k", "10", str(limit_s), "rocprofv3", "--kernel-trace", "--output-format", "csv", "-d", tmp, "-o", "t", "--",
-                   sys.executable, os.path.abspath(__file__), "--case", name]
+                   sys.executable, os.path.abspath(script), "--case", name]
             r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
             if r.returncode != 0:
                 sys.exit("case %s: exit status %d -- stopping here\n%s" % (name, r.returncode, r.stdout[-3000:]))
@@ -100,12 +101,13 @@ def collect(out_path, names, limit_s=180):
         json.dump(res, open(out_path, "w"), indent=0)
 
 
-def report(a_path, b_path):
+def report(a_path, b_path, cases=None):
+    cases = cases or CASES
     A, B = json.load(open(a_path)), json.load(open(b_path))
     sha = lambda ls: hashlib.sha256(json.dumps(ls).encode()).hexdigest()[:16]
-    names = [n for n in CASES if n in A and n in B]
+    names = [n for n in cases if n in A and n in B]
     same = all(A[n]["launches"] == B[n]["launches"] and A[n]["calls"] == B[n]["calls"] for n in names)
-    print("# %d of %d cases, parent and new lists %s" % (len(names), len(CASES), "IDENTICAL in every case" if same else "DIFFER"))
+    print("# %d of %d cases, parent and new lists %s" % (len(names), len(cases), "IDENTICAL in every case" if same else "DIFFER"))
     for name in names:
         a, b = A[name]["launches"], B[name]["launches"]
         print("== %s: %d launches, sha256 %s (parent) %s %s (new)" % (name, len(b), sha(a), "=" if a == b else "!=", sha(b)))
