@@ -34,8 +34,15 @@ from .convex_adam_MIND import extract_features as _extract_features
 from .convex_adam_nnUNet import extract_features as _extract_features_nnunet
 from .rigid import find_rigid_3d, least_trimmed_rigid  # noqa: F401  (self_configuring/convexAdam_hyper_util.py:326-346)
 from .ssim import create_window_3D, gaussian, registration_ssim, ssim3D, ssim3D_map  # noqa: F401  (tests/helper_functions.py:102-145)
+from .prep import (compute_steps_for_sliding_window, create_nonzero_mask, crop_to_bbox, get_bbox_from_mask, nnUNetCTnorm, nnUNetNorm,  # noqa: F401
+                   nnUNetNormProps, normalise_and_crop, pdist_squared, get_gaussian as _get_gaussian)     # (self_configuring/convexAdam_hyper_util.py:295-420)
 from .l2r3 import (SAVE_PATHS, aggregate_cases, critical_u2, experiment_key, greaters, mind_parameters, options_for, parse_winner,  # noqa: F401
                    rank_experiments, rankscore_avgtie, ranksum_better, ranksum_statistic, scores_better, self_configure)     # (self_configuring/l2r3.py:223-375)
+
+
+def get_gaussian(patch_size, sigma_scale=1. / 8):
+    """hyper_util.py:378-391: no device argument there, the table goes to the HIP device."""
+    return _get_gaussian(patch_size, sigma_scale, device='cuda')
 
 
 def MINDSSC(img, radius=2, dilation=2):

@@ -8,6 +8,8 @@ Same names, argument meaning and return formats as the reference:
     inverse_consistency convex_adam_utils.py:114-129
     combineDeformation3d convex_adam_utils.py:133-135
     validate_image      convex_adam_utils.py:268-279
+    pdist_squared, nnUNetNorm, nnUNetNormProps, nnUNetCTnorm, compute_steps_for_sliding_window, get_gaussian,
+    create_nonzero_mask, get_bbox_from_mask, crop_to_bbox        convex_adam_utils.py:15-21, 142-170, 196-265   (prep.py)
 Tensors must live on the HIP device (torch device type 'cuda'); the kernels compute in float32 and
 results are cast back to the dtype the reference would return.  There is no CPU fallback.
 """
@@ -495,3 +497,6 @@ from .geometry import (Grid, field_mean_device, grid_of, index_map, register_ima
 # a cropped-grid field carried to the original fixed grid at half resolution (l2r_2021_convexAdam_task1_docker.py:38-105,390-400): csrc/cropfield.hip
 from .cropfield import (CropCase, convert_crop_field, half_resolution_field, physical_displacement, read_cases,  # noqa: E402,F401
                         submission_field)
+# the nnU-Net preprocessing helpers (convex_adam_utils.py:15-21,142-170,196-265): csrc/prep.hip
+from .prep import (compute_steps_for_sliding_window, create_nonzero_mask, crop_to_bbox, get_bbox_from_mask, get_gaussian,  # noqa: E402,F401
+                   nnUNetCTnorm, nnUNetNorm, nnUNetNormProps, normalise_and_crop, pdist_squared)
