@@ -500,3 +500,5 @@ from .cropfield import (CropCase, convert_crop_field, half_resolution_field, phy
 # the nnU-Net preprocessing helpers (convex_adam_utils.py:15-21,142-170,196-265): csrc/prep.hip
 from .prep import (compute_steps_for_sliding_window, create_nonzero_mask, crop_to_bbox, get_bbox_from_mask, get_gaussian,  # noqa: E402,F401
                    nnUNetCTnorm, nnUNetNorm, nnUNetNormProps, normalise_and_crop, pdist_squared)
+# the opposite direction of a result -- inverse and composition of displacement fields (no counterpart in the reference): csrc/fieldops.hip
+from .fieldops import apply_convex_inverse, compose_fields, invert_field  # noqa: E402,F401
