@@ -106,7 +106,7 @@ __global__ __launch_bounds__(BT_NT) void k_box3x3(const float* __restrict__ in, 
     const float* ic = in + (size_t)c * V;
     // stage columns x0-4 .. x0+35 (LDS columns 4..43) of rows z0-3.., y0-3..; zero outside the volume
     constexpr int AZ = BT_Z + 6, AY = BT_Y + 6, NCH = (BT_X + 8) / 4;
-    const bool vec = (d & 3) == 0;
+    const bool vec = (d & 3) == 0 && ((uintptr_t)in & 15) == 0;       // (uniform) rows of whole quads from a 16-byte aligned volume
     for (int i = threadIdx.x; i < AZ * AY * NCH; i += BT_NT) {
         const int ch = i % NCH, y = (i / NCH) % AY, z = i / (NCH * AY);
         const int gz = z0 - 3 + z, gy = y0 - 3 + y, gx = x0 - 4 + 4 * ch;

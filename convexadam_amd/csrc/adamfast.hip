@@ -239,7 +239,9 @@ __global__ __launch_bounds__(256) void k_box3_fast(const float* __restrict__ in,
     const int x0 = tx * TX, y0 = ty * TY, z0 = tz * TZ;
     const size_t V = (size_t)h * w * d;
     const float* ic = in + (size_t)c * V;
-    const bool vec = (d & 3) == 0;
+    // 16-byte accesses: rows of whole quads AND every volume the epilogue touches 16-byte aligned (uniform: kernel arguments; V % 4 == 0 with d,
+    // so the channels keep the base's alignment); anything else takes the 4-byte arms below
+    const bool vec = (d & 3) == 0 && (((uintptr_t)out | (uintptr_t)P | (uintptr_t)m | (uintptr_t)v | (uintptr_t)gsave) & 15) == 0;
     float* oc = out ? out + (size_t)c * V : nullptr;
     float* Pc = ADAM ? P + (size_t)c * V : nullptr;
     float* mc = ADAM ? m + (size_t)c * V : nullptr;

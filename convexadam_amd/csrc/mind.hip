@@ -233,7 +233,7 @@ __global__ __launch_bounds__(TX / RUN * TY * TZ) void k_mind(const float* __rest
     // raw patch-SSDs -> out, already in the final channel order (normalised in place by k_mind_finish)
     if (gz < H && gy < W) {
         const int gx0 = x0 + tx0;
-        const bool vec = ((D & 3) == 0) && (gx0 + RUN <= D);
+        const bool vec = ((D & 3) == 0) && ((reinterpret_cast<uintptr_t>(out) & 15) == 0) && (gx0 + RUN <= D);      // (V % 4 == 0 with D: every channel as aligned as `out`)
 #pragma unroll
         for (int c = 0; c < 12; ++c) {
             float* dst = out + (size_t)MIND_INV[c] * V + ((size_t)gz * W + gy) * D + gx0;

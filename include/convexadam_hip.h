@@ -17,6 +17,11 @@
  *   - `stream` is a hipStream_t passed as void* (NULL = default stream); calls enqueue work and
  *     return without synchronising; nothing is allocated: the caller supplies outputs and a
  *     scratch workspace whose size comes from the matching *_workspace_bytes() query;
+ *   - data operands need only the alignment of their element type (4 bytes for float32 and int32, 8 for float64 and int64, 2 for half
+ *     precision, 1 for bytes) unless the entry point's own comment says otherwise; a workspace or scratch base must be 256-byte
+ *     aligned.  Kernels with 8- or 16-byte accesses are chosen from the pointers' low bits and give the same bits as the element-wise
+ *     ones.  Entry points that say otherwise: cvx_mindssc_pooled_f32 (an image that is not 16-byte aligned needs the two-pass
+ *     scratch), cvx_crop_field_half_f32 and cvx_ranksum_better_f64 (a buffer not aligned to its element is refused);
  *   - return value 0 = ok, negative = CVX_ERR_*; cvx_last_error() gives a thread-local message;
  *   - floating-point evaluation order follows the ATen CPU kernels the reference calls, so results
  *     are reproducible bit-for-bit against the CPU oracle (oracle/cvx_oracle.c);

@@ -3,7 +3,11 @@ exists for are each reported by check_fences; the well-behaved one is not.  With
 
 The fake operators reach outside their operand through the view's storage, as a kernel does through its pointer.  On a plain allocation
 (storage offset 0, nothing behind the last element) the stray access has nowhere to go and is skipped: there it would land in the
-allocator's slack, which is exactly why the plain run cannot see it."""
+allocator's slack, which is exactly why the plain run cannot see it.
+
+The second half does the same for fenced(.., shift=) and check_unaligned(): a shifted payload sits where it should, the moat checks still
+catch a store one element before and one element behind it, and a refusal is accepted only from an operator with the right to refuse.
+(check_side_stream needs a device: tests/test_gpu_placement_selftest.py.)"""
 import os
 import sys
 
@@ -12,7 +16,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import fences  # noqa: E402
-from fences import IN, INOUT, OUT, SCRATCH, check_fences, fenced  # noqa: E402
+from fences import IN, INOUT, OUT, SCRATCH, check_fences, check_unaligned, fenced  # noqa: E402
 
 DEV = "cpu"
 
@@ -120,3 +124,93 @@ def test_misbehaving_operator_is_reported(op, needle):
 def test_failed_call_is_reported():
     with pytest.raises(AssertionError, match="returned -2"):
         check_fences(operands(), lambda t: -2, DEV)
+
+
+# ---- shifted payloads (check_unaligned) ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dtype,n", [(torch.float32, 4), (torch.float32, 12), (torch.float64, 8), (torch.int64, 24), (torch.float16, 2), (torch.float16, 18),
+                                     (torch.uint8, 1), (torch.uint8, 17), (torch.float32, 0)])
+def test_shifted_layout(dtype, n):
+    plain = fenced((3, 5, 7), dtype, DEV, None)
+    v = fenced((3, 5, 7), dtype, DEV, None, shift=n)
+    f, f0 = v.fence, plain.fence
+    assert v.shape == (3, 5, 7) and v.is_contiguous()
+    assert f.lo == f0.lo + n and f.nbytes == f0.nbytes and (v.data_ptr() - f.raw.data_ptr()) == f.lo
+    assert f.lo % 256 == n and f.lo % 16 == n % 16
+    assert f.raw.numel() % 256 == 0 and f.raw.numel() - f.lo - f.nbytes >= f0.lo          # both moats as large as without the shift
+    v.fill_(1)
+    assert int((f.raw != 0xA5).sum()) == f.nbytes and bool((f.payload() != 0xA5).all())
+
+
+def test_shifted_layout_keeps_the_typed_moat_fill():
+    v = fenced((5, 3), torch.float32, DEV, float("nan"), shift=4)
+    whole = v.fence.raw.view(torch.float32)
+    assert bool(torch.isnan(whole).all())
+    v.fill_(0.0)
+    assert int((~torch.isnan(whole)).sum()) == 15
+    with pytest.raises(AssertionError, match="whole elements"):
+        fenced((5, 3), torch.float32, DEV, 0, shift=2)
+    with pytest.raises(AssertionError, match="whole elements"):
+        fenced((5, 3), torch.uint8, DEV, 0, shift=256)
+
+
+ALL = ("x", "idx", "y", "state")
+
+
+def test_well_behaved_operator_passes_unaligned():
+    for which in (ALL, ("x",), ("y",), ("state",), ()):
+        ts, how = check_unaligned(operands(), op_good, DEV, which)
+        assert how == "ran"
+        for k in ALL:
+            assert ts[k].fence.lo % 256 == (4 if k in which else 0)
+
+
+@pytest.mark.parametrize("op,which,needle", [
+    (op_store_before, ALL, "of out operand 'y' changed, the first 4 byte(s) before its payload"),
+    (op_store_after, ALL, "of out operand 'y' changed, the first 1 byte(s) behind its payload"),
+    (op_store_before, ("y",), "before its payload"),
+    (op_store_before_inout, ALL, "inout operand 'state'"),
+    (op_read_past_input, ALL, "differs from the aligned plain run in out 'y'"),
+    (op_skips_one, ALL, "differs from the aligned plain run in out 'y': first at byte 20"),
+    (op_writes_input, ALL, "input 'x' was modified"),
+])
+def test_misbehaving_operator_is_reported_unaligned(op, which, needle):
+    with pytest.raises(AssertionError) as e:
+        check_unaligned(operands(), op, DEV, which)
+    assert needle in str(e.value), str(e.value)
+
+
+def op_takes_a_wide_path_blindly(t):
+    """what an unguarded 16-byte kernel does to a misaligned output in the worst case: it rounds the address down"""
+    op_good(t)
+    if t["y"].data_ptr() % 16:
+        e = outside(t["y"], -1)
+        if e is not None:
+            e.copy_(t["y"].view(-1)[:1])
+
+
+def test_rounded_down_address_is_reported():
+    check_fences(operands(), op_takes_a_wide_path_blindly, DEV)                 # aligned payloads: nothing to see
+    with pytest.raises(AssertionError, match="before its payload"):
+        check_unaligned(operands(), op_takes_a_wide_path_blindly, DEV, ("y",))
+
+
+def test_refusal_is_accepted_only_with_the_right_to_refuse():
+    def refuses(t):
+        return -1 if t["x"].data_ptr() % 16 else (op_good(t) or 0)
+    with pytest.raises(AssertionError, match="the call returned -1"):
+        check_unaligned(operands(), refuses, DEV, ALL)
+    ts, how = check_unaligned(operands(), refuses, DEV, ALL, refusal=(-1, lambda: "x is not aligned to 16 bytes"))
+    assert how == "refused"
+    with pytest.raises(AssertionError, match="does not name the alignment"):
+        check_unaligned(operands(), refuses, DEV, ALL, refusal=(-1, lambda: "bad argument"))
+
+    def refuses_late(t):
+        op_good(t)
+        return -1 if t["x"].data_ptr() % 16 else 0
+    with pytest.raises(AssertionError, match="a refused call wrote output 'y'"):
+        check_unaligned(operands(), refuses_late, DEV, ALL, refusal=(-1, lambda: "not aligned"))
+
+
+def test_scratch_is_never_shifted():
+    with pytest.raises(AssertionError, match="never shifted"):
+        check_unaligned(operands(), op_good, DEV, ("ws",))
