@@ -649,16 +649,11 @@ static void cert_arm(CertArgs& A, int nprob, hipStream_t s) {
 static void cert_stream(CertArgs A, int q0, int nq, hipStream_t s) {
     const CertGeo& g = A.g;
     const size_t v = (size_t)g.h * g.w * g.d;
-    const int K = g.K;
     if (q0) { A.p[0] = A.p[q0]; }
     bool vec4 = v % 4 == 0;
     for (int q = 0; q < nq; ++q) vec4 = vec4 && (reinterpret_cast<uintptr_t>(A.p[q].ssdu) & 15) == 0;
     const int xb = (int)cdiv64((int64_t)cdiv64((int64_t)v, 4), 256);
-    int nslices = cdiv(512, xb);
-    if (nslices > K) nslices = K;
-    if (nslices < 1) nslices = 1;
-    const int kslice = cdiv(K, nslices);
-    nslices = cdiv(K, kslice);
+    const auto [kslice, nslices] = k_slices(xb, 512, g.K);
     hipLaunchKernelGGL(k_cert_plain_stream, dim3(xb, nslices, nq), dim3(256), 0, s, A, kslice, vec4 ? 1 : 0);
 }
 static int cert_finish(CertArgs& A, int nprob, hipStream_t s) {
@@ -692,7 +687,7 @@ int corr_certified_argmin(const float* ssdu, const float* fix, const float* mov,
 // 5 = the coupled passes (the pipeline interleaves 2 / 3 with the correlation kernels: each volume is streamed from the Infinity Cache)
 int coupled_convex_cert_impl(const float* ssduA, const float* fixA, const float* movA, float* outA, void* wsA, const float* ssduB, const float* fixB,
                              const float* movB, float* outB, void* wsB, const float* mesh, int C, int h, int w, int d, int hw, size_t workspace_bytes,
-                             hipStream_t s, int stage) {
+                             int refine, hipStream_t s, int stage) {
     if (workspace_bytes < corr_certify_workspace_bytes(C, h, w, d, hw, false)) return fail(CVX_ERR_WORKSPACE, "certified coupled convex: workspace too small");
     const int nprob = ssduB ? 2 : 1;
     CertArgs A{};
@@ -709,10 +704,8 @@ int coupled_convex_cert_impl(const float* ssduA, const float* fixA, const float*
     if (stage == 4) return cert_finish(A, nprob, s);
     if (stage == 0) { const int rc = cert_plain(A, nprob, true, s); if (rc) return rc; }
     const size_t v = (size_t)h * w * d;
-    const int refine = options().prune_refine != 0 ? 8 : 0x7fffffff;
-    static const float coeffs[6] = {0.003f, 0.01f, 0.03f, 0.1f, 0.3f, 1.0f};      // torch.tensor([...]) float32 (:98)
     for (int it = 0; it < 6; ++it) {
-        A.coef = coeffs[it]; A.pass = it + 1;
+        A.coef = kCoupledCoeffs[it]; A.pass = it + 1;
         hipLaunchKernelGGL(k_cert_voxel, dim3((unsigned)cdiv64((int64_t)v, 64), nprob), dim3(64), 0, s, A, refine);
         hipLaunchKernelGGL(k_cert_wave, dim3(512, nprob), dim3(256), 0, s, A);
     }

@@ -502,11 +502,7 @@ static int argmin_pass(const ST* ssd, const float* mesh, const float* u, float c
     const int xb = (int)cdiv64((int64_t)(vec4 ? v / 4 : v), 256);
     // about 512 workgroups (2 per CU): every K-slice ends in one atomicMin per voxel, and 450-650 workgroups measured fastest on
     // the 270 MB volume (52 us = 5.2 TB/s; 1024: 64 us, 256: 56 us, 2048: 75 us)
-    int nslices = cdiv(vec4 ? 512 : 1024, xb);
-    if (nslices > K) nslices = K;
-    if (nslices < 1) nslices = 1;
-    const int kslice = cdiv(K, nslices);
-    nslices = cdiv(K, kslice);
+    const auto [kslice, nslices] = k_slices(xb, vec4 ? 512 : 1024, K);
     const dim3 grid(xb, nslices);
     if (vec4) {
         if (coupled) hipLaunchKernelGGL((k_argmin4<true, ST>), grid, dim3(256), 0, s, ssd, mesh, u, coef, K, v, kslice, keys, cmask);
@@ -520,28 +516,27 @@ static int argmin_pass(const ST* ssd, const float* mesh, const float* u, float c
 // large boxes; kprev = int32 indices (first pass) or the key buffer of the previous pass; *list_count must be zero on entry
 // (the previous pass's voxel kernel clears it through next_count; the two counters alternate)
 template <typename PrevT, typename ST>
-static int argmin_pass_pruned(const ST* ssd, const float* mesh, float* u, float coef, int K, int n, int h, int w, int d,
-                              const float* smin, const PrevT* kprev, unsigned long long* list, int* list_count, int* next_count,
-                              unsigned long long* keys, const unsigned long long* minkeys, const Prob2& o, int nprob, hipStream_t s,
-                              const unsigned char* cmask) {
+static int argmin_pass_pruned(const CoupledPlan& pl, const ST* ssd, const float* mesh, float* u, float coef, const float* smin, const PrevT* kprev,
+                              unsigned long long* list, int* list_count, int* next_count, unsigned long long* keys,
+                              const unsigned long long* minkeys, const Prob2& o, hipStream_t s, const unsigned char* cmask) {
+    const int h = pl.u.h, w = pl.u.w, d = pl.u.d, n = 2 * pl.u.disp_hw + 1, K = n * n * n;
     const size_t v = (size_t)h * w * d;
-    const int refine = options().prune_refine != 0 ? 8 : 0x7fffffff;     // boxes above the per-thread limit get the second bound
-    hipLaunchKernelGGL((k_argmin_voxel<PrevT, ST>), dim3((unsigned)cdiv64((int64_t)v, 64), nprob), dim3(64), 0, s, ssd, mesh, u, coef, K, n, h,
-                       w, d, smin, kprev, 8, list, list_count, next_count, keys, minkeys, refine, o, cmask);   // limit 8 = NB of the voxel kernel
-    // worst case bounded by one coalesced scan per pass: a chunk of 256 scattered reads moves about 8 KB, the scan K * v * 4 bytes
-    const long long above = options().prune_stream_above >= 0 ? options().prune_stream_above : (long long)((double)K * (double)v / 2048.0);
-    const int stream_above = (int)(above > 0x7fffffff ? 0x7fffffff : above);
+    hipLaunchKernelGGL((k_argmin_voxel<PrevT, ST>), dim3((unsigned)cdiv64((int64_t)v, 64), pl.nprob), dim3(64), 0, s, ssd, mesh, u, coef, K, n, h,
+                       w, d, smin, kprev, 8, list, list_count, next_count, keys, minkeys, pl.refine, o, cmask);   // limit 8 = NB of the voxel kernel
     const int vec = (v % 4 == 0) && ((reinterpret_cast<uintptr_t>(ssd) | (uintptr_t)(o.ssd < 0 ? -o.ssd : o.ssd)) & 15) == 0;
     // voxels whose key the voxel kernel stored plainly keep it under the scan (it finds the same winner); listed voxels were armed to ~0
-    hipLaunchKernelGGL((k_argmin_wave<PrevT, ST>), dim3(512, nprob), dim3(256), 0, s, ssd, mesh, u, coef, K, n, v, smin, kprev, list,
-                       list_count, keys, stream_above, vec, refine, o, cmask);
+    hipLaunchKernelGGL((k_argmin_wave<PrevT, ST>), dim3(512, pl.nprob), dim3(256), 0, s, ssd, mesh, u, coef, K, n, v, smin, kprev, list,
+                       list_count, keys, pl.stream_above, vec, pl.refine, o, cmask);
     return check_last("argmin_pruned");
 }
 
 // plain argmin pass that leaves its (cost, index) keys in `keys` (first key buffer of a coupled-convex workspace)
-int launch_argmin_keys(const void* ssd, bool f16, int K, size_t v, unsigned long long* keys, bool arm, hipStream_t s) {
-    if (f16) return argmin_pass(static_cast<const __half*>(ssd), nullptr, nullptr, 0.0f, false, K, v, keys, arm, s);
-    return argmin_pass(static_cast<const float*>(ssd), nullptr, nullptr, 0.0f, false, K, v, keys, arm, s);
+// f(typed volume pointer): the one place where the element type of a cost volume becomes a template argument
+template <typename F>
+static int with_volume_type(bool f16, const void* ssd, F&& f) { return f16 ? f(static_cast<const __half*>(ssd)) : f(static_cast<const float*>(ssd)); }
+
+int launch_argmin_keys(const void* ssd, bool f16, int K, size_t v, unsigned long long* keys, hipStream_t s) {
+    return with_volume_type(f16, ssd, [&](auto* p) { return argmin_pass(p, nullptr, nullptr, 0.0f, false, K, v, keys, false, s); });
 }
 CoupledWs coupled_layout(Carver& cv, int h, int w, int d, int disp_hw) {
     const int n = 2 * disp_hw + 1, K = n * n * n;
@@ -558,8 +553,7 @@ CoupledWs coupled_layout(Carver& cv, int h, int w, int d, int disp_hw) {
 
 int launch_argmin(const void* ssd, bool f16, const float* mesh, const float* u, float coef, bool coupled, int K, size_t v,
                   unsigned long long* keys, int64_t* argmin_out, hipStream_t s) {
-    int rc = f16 ? argmin_pass(static_cast<const __half*>(ssd), mesh, u, coef, coupled, K, v, keys, true, s)
-                 : argmin_pass(static_cast<const float*>(ssd), mesh, u, coef, coupled, K, v, keys, true, s);
+    int rc = with_volume_type(f16, ssd, [&](auto* p) { return argmin_pass(p, mesh, u, coef, coupled, K, v, keys, true, s); });
     if (rc) return rc;
     hipLaunchKernelGGL(k_keys_to_index, dim3((unsigned)cdiv64((int64_t)v, 256)), dim3(256), 0, s, keys, v, (int*)nullptr,
                        argmin_out);
@@ -721,28 +715,62 @@ extern "C" int cvx_coupled_convex_masked_f32(const float* ssd, const int64_t* ar
                                              void* stream) {
     // the caller's `argmin` only seeds the first smoothing step (as in the reference); the lower bound of the pruned
     // passes is taken from the (masked) volume itself
-    return cvx::coupled_convex_impl(ssd, false, argmin, mesh, h, w, d, disp_hw, out, /*argmin_is_exact=*/false, workspace, workspace_bytes, stream,
-                                    cell_mask);
+    return cvx::coupled_convex_impl(ssd, false, argmin, mesh, h, w, d, disp_hw, out, workspace, workspace_bytes, stream, cell_mask);
 }
 
 extern "C" int cvx_coupled_convex_f16(const void* ssd_half, const int64_t* argmin, const float* mesh, int h, int w, int d,
                                       int disp_hw, float* out, void* workspace, size_t workspace_bytes, void* stream) {
-    return cvx::coupled_convex_impl(ssd_half, true, argmin, mesh, h, w, d, disp_hw, out, /*argmin_is_exact=*/false, workspace, workspace_bytes, stream);
+    return cvx::coupled_convex_impl(ssd_half, true, argmin, mesh, h, w, d, disp_hw, out, workspace, workspace_bytes, stream, nullptr);
 }
 
-// argmin_is_exact: `argmin` is the plain argmin of `ssd` (the whole-pair pipeline computes it itself), so ssd[argmin] is the
-// per-voxel minimum and the extra streaming pass that determines it can be skipped.
-// nprob = 2: a second, independent problem (displaced by `o`, see Prob2) is solved by the same launches.
+// ---- how the stage runs: ONE plan per call, read by coupled_core, the whole-pair pipeline (PairRun) and certify.hip -----------------------
+// Options are read here and nowhere else in the stage: no_prune, prune_refine, prune_stream_above (of the context bound to the call).
+//   use                                 | no_prune = 0 (Pruned)                                          | no_prune = 1 (Streamed)
+//   winners, not vouched (the three     | seed Indices, smin OwnMinPass (keys[0], cell mask applied),    | seed Indices, smin None, minkeys no,
+//     operators, the masked stage)      |   minkeys yes, prep CallerWinners, nprob 1                     |   prep CallerWinners, nprob 1
+//   winners, vouched (no caller today)  | seed Indices, smin GatherAtSeed (ssd[idx]), minkeys no,        | as above
+//                                       |   prep CallerWinners, nprob as offered                         |
+//   no winners, vouched (whole pair:    | seed Keys, smin FromKeys (one launch gives idx and smin),      | seed Indices, smin None, minkeys no,
+//     it runs the plain argmin itself)  |   minkeys yes, prep Keys, nprob as offered                     |   prep Winners64, nprob 1
+//   no winners, not vouched             | invalid KeysNeedPruned: nothing says what keys[0] holds        | the same
+//   masked and (vouched, no winners or  | invalid MaskNeedsOwnMin (tested first): the plain argmin of the UNMASKED volume says nothing about the
+//     two problems)                     |   masked one's minima, and the mask is one problem's           | the same
+//   Streamed, two problems offered: sequential = true, two solves of one problem each (the streamed kernels take no second problem).
+//   prep says what an asker without winners does before the solve: Keys = launch_argmin_keys(arm = false) into keys[0], which it set to all
+//   ones, and both list lengths zero (k_pair_setup); Winners64 = launch_argmin, which arms keys[0] itself, int64 winners handed over.
+//   A plan with seed Indices and no `argmin` pointer is refused by coupled_core with the KeysNeedPruned text (it is how that state arose).
+//   refine = 8 (boxes above the per-thread limit get the second bound) or INT_MAX with prune_refine = 0; stream_above = the option, or
+//   K v / 2048 if it is negative (a chunk of 256 scattered reads moves about 8 KB, the scan K v 4 bytes), at most INT_MAX.
+CoupledPlan cvx::coupled_plan(const CoupledUse& u) {
+    const Options& o = options();
+    CoupledPlan p{};
+    p.u = u;
+    p.invalid = u.masked && (u.vouched || !u.winners || u.nprob != 1) ? CoupledInvalid::MaskNeedsOwnMin
+                : !u.winners && !u.vouched                               ? CoupledInvalid::KeysNeedPruned
+                                                                         : CoupledInvalid::No;
+    p.passes = o.no_prune != 0 ? CoupledPasses::Streamed : CoupledPasses::Pruned;
+    const bool pruned = p.passes == CoupledPasses::Pruned;
+    p.seed = pruned && !u.winners ? CoupledSeed::Keys : CoupledSeed::Indices;
+    p.smin = !pruned ? CoupledSmin::None : !u.winners ? CoupledSmin::FromKeys : u.vouched ? CoupledSmin::GatherAtSeed : CoupledSmin::OwnMinPass;
+    p.minkeys = p.smin == CoupledSmin::FromKeys || p.smin == CoupledSmin::OwnMinPass;
+    p.nprob = pruned ? u.nprob : 1;
+    p.sequential = !pruned && u.nprob == 2;
+    p.prep = u.winners ? CoupledPrep::CallerWinners : pruned ? CoupledPrep::Keys : CoupledPrep::Winners64;
+    p.refine = o.prune_refine != 0 ? 8 : 0x7fffffff;
+    const int n = 2 * u.disp_hw + 1;
+    const long long above = o.prune_stream_above >= 0 ? o.prune_stream_above : (long long)((double)n * n * n * ((double)u.h * u.w * u.d) / 2048.0);
+    p.stream_above = (int)(above > 0x7fffffff ? 0x7fffffff : above);
+    return p;
+}
+
+// pl.nprob = 2: a second, independent problem (displaced by `o`, see Prob2) is solved by the same launches.
 template <typename ST>
-static int coupled_core(const ST* ssd, const int64_t* argmin, const float* mesh, int h, int w, int d, int disp_hw, float* out,
-                        bool argmin_is_exact, void* workspace, size_t workspace_bytes, const Prob2& o, int nprob, void* stream,
-                        bool counts_zeroed = false, const unsigned char* cmask = nullptr) {
-    // argmin == nullptr: the (cost, index) keys of the plain argmin pass sit in the first key buffer of the workspace
-    const bool from_keys = argmin == nullptr;
+static int coupled_core(const CoupledPlan& pl, const ST* ssd, const int64_t* argmin, const float* mesh, float* out, void* workspace,
+                        size_t workspace_bytes, const Prob2& o, void* stream, const unsigned char* cmask) {
+    const int h = pl.u.h, w = pl.u.w, d = pl.u.d, disp_hw = pl.u.disp_hw;
     CVX_REQUIRE(ssd && mesh && out && workspace, "cvx_coupled_convex_f32: null pointer");
     CVX_REQUIRE(h > 0 && w > 0 && d > 0 && disp_hw >= 0, "cvx_coupled_convex_f32: bad arguments");
-    // a cell mask: the plain argmin of the UNMASKED volume says nothing about the masked one's minima, and the mask is one problem's
-    CVX_REQUIRE(!cmask || (!argmin_is_exact && argmin && nprob == 1), "coupled_convex: a cell mask needs the library's own minimum pass");
+    CVX_REQUIRE(pl.invalid != CoupledInvalid::MaskNeedsOwnMin, "coupled_convex: a cell mask needs the library's own minimum pass");
     if (workspace_bytes < cvx_coupled_convex_workspace_bytes(h, w, d, disp_hw))
         return fail(CVX_ERR_WORKSPACE, "cvx_coupled_convex_f32: workspace too small");
     hipStream_t s = as_stream(stream);
@@ -750,35 +778,30 @@ static int coupled_core(const ST* ssd, const int64_t* argmin, const float* mesh,
     const size_t v = (size_t)h * w * d;
     Carver cv(workspace);
     // three key buffers in rotation: pass p mins into keys[p % 3]; the gather that consumes pass p re-arms keys[(p+2) % 3]
-    const auto [keys, idx, smin, list, list_count] = coupled_layout(cv, h, w, d, disp_hw);
-    const dim3 gv((unsigned)cdiv64((int64_t)v, 256), nprob);
-    const bool no_prune_env = options().no_prune != 0;
-    if (from_keys && (no_prune_env || !argmin_is_exact)) return fail(CVX_ERR_INVALID_ARG, "coupled_convex: key input needs the pruned path");
+    const auto [keys, idx, smin, list, counts] = coupled_layout(cv, h, w, d, disp_hw);      // counts: two alternating list lengths
+    const dim3 gv((unsigned)cdiv64((int64_t)v, 256), pl.nprob);
+    const bool from_keys = pl.seed == CoupledSeed::Keys;
+    if (pl.invalid == CoupledInvalid::KeysNeedPruned || (!from_keys && !argmin)) return fail(CVX_ERR_INVALID_ARG, "coupled_convex: key input needs the pruned path");
     if (!from_keys) hipLaunchKernelGGL(k_index64_to_32, gv, dim3(256), 0, s, argmin, v, idx, o);
-    // exact pruning needs smin[x] = min_k ssd[k,x].  CVX_NO_PRUNE=1 streams every pass instead.
-    const bool no_prune = options().no_prune != 0;
-    const bool prune = !no_prune;
-    if (prune) {
-        int* counts = list_count;                                       // two alternating list lengths
-        for (int q = 0; q < nprob && !counts_zeroed; ++q)
+    if (pl.passes == CoupledPasses::Pruned) {
+        // exact pruning needs smin[x] = min_k ssd[k,x]
+        for (int q = 0; q < pl.nprob && pl.prep != CoupledPrep::Keys; ++q)
             if (hipMemsetAsync(reinterpret_cast<char*>(counts) + (q ? o.ws : 0), 0, 2 * sizeof(int), s) != hipSuccess)
                 return fail(CVX_ERR_LAUNCH, "coupled_convex: memset failed");
-        if (from_keys) hipLaunchKernelGGL(k_keys_to_idx_min, gv, dim3(256), 0, s, keys[0], v, idx, smin, o);
-        else if (argmin_is_exact) hipLaunchKernelGGL(k_gather_min<ST>, gv, dim3(256), 0, s, ssd, idx, v, smin, o);
+        if (pl.smin == CoupledSmin::FromKeys) hipLaunchKernelGGL(k_keys_to_idx_min, gv, dim3(256), 0, s, keys[0], v, idx, smin, o);
+        else if (pl.smin == CoupledSmin::GatherAtSeed) hipLaunchKernelGGL(k_gather_min<ST>, gv, dim3(256), 0, s, ssd, idx, v, smin, o);
         else {
             int rc = argmin_pass(ssd, nullptr, nullptr, 0.0f, false, K, v, keys[0], true, s, cmask);   // per-voxel minimum of the volume (a masked-out column: 0 at index 0)
             if (rc) return rc;
             hipLaunchKernelGGL(k_keys_to_min, dim3(gv.x), dim3(256), 0, s, keys[0], v, smin);
         }
-        static const float coeffs[6] = {0.003f, 0.01f, 0.03f, 0.1f, 0.3f, 1.0f};   // torch.tensor([...]) float32 (:98)
+        const unsigned long long* minkeys = pl.minkeys ? keys[0] : nullptr;
         for (int it = 0; it < 6; ++it) {
             // smoothing of the previous winners + pruned argmin; keys[1], keys[2] alternate (keys[0] may hold the minimum pass)
             unsigned long long* kc = keys[1 + (it & 1)];
             int rc;
-            // keys[0] holds the library's own minimum pass unless the caller vouched for `argmin` (then idx IS the plain argmin)
-            const unsigned long long* minkeys = (from_keys || !argmin_is_exact) ? keys[0] : nullptr;
-            if (it == 0) rc = argmin_pass_pruned<int, ST>(ssd, mesh, out, coeffs[it], K, n, h, w, d, smin, idx, list, counts + (it & 1), counts + ((it + 1) & 1), kc, minkeys, o, nprob, s, cmask);
-            else rc = argmin_pass_pruned<unsigned long long, ST>(ssd, mesh, out, coeffs[it], K, n, h, w, d, smin, keys[1 + ((it - 1) & 1)], list, counts + (it & 1), counts + ((it + 1) & 1), kc, minkeys, o, nprob, s, cmask);
+            if (it == 0) rc = argmin_pass_pruned<int, ST>(pl, ssd, mesh, out, kCoupledCoeffs[it], smin, idx, list, counts + (it & 1), counts + ((it + 1) & 1), kc, minkeys, o, s, cmask);
+            else rc = argmin_pass_pruned<unsigned long long, ST>(pl, ssd, mesh, out, kCoupledCoeffs[it], smin, keys[1 + ((it - 1) & 1)], list, counts + (it & 1), counts + ((it + 1) & 1), kc, minkeys, o, s, cmask);
             if (rc) return rc;
         }
         hipLaunchKernelGGL(k_gather_box3<unsigned long long>, gv, dim3(256), 0, s, keys[1 + (5 & 1)], mesh, K, h, w, d, out, (unsigned long long*)nullptr, (int*)nullptr, o);
@@ -787,9 +810,8 @@ static int coupled_core(const ST* ssd, const int64_t* argmin, const float* mesh,
     // streaming path: one problem per call
     if (hipMemsetAsync(keys[0], 0xff, sizeof(unsigned long long) * v, s) != hipSuccess) return fail(CVX_ERR_LAUNCH, "coupled_convex: memset failed");
     hipLaunchKernelGGL(k_gather_box3<int>, dim3(gv.x), dim3(256), 0, s, idx, mesh, K, h, w, d, out, keys[1], (int*)nullptr, o);
-    static const float coeffs[6] = {0.003f, 0.01f, 0.03f, 0.1f, 0.3f, 1.0f};   // torch.tensor([...]) float32 (:98)
     for (int it = 0; it < 6; ++it) {
-        int rc = argmin_pass(ssd, mesh, out, coeffs[it], true, K, v, keys[it % 3], false, s, cmask);
+        int rc = argmin_pass(ssd, mesh, out, kCoupledCoeffs[it], true, K, v, keys[it % 3], false, s, cmask);
         if (rc) return rc;
         // the streamed passes need their key buffer re-armed two passes ahead
         hipLaunchKernelGGL(k_gather_box3<unsigned long long>, dim3(gv.x), dim3(256), 0, s, keys[it % 3], mesh, K, h, w, d, out,
@@ -799,37 +821,36 @@ static int coupled_core(const ST* ssd, const int64_t* argmin, const float* mesh,
 }
 
 int cvx::coupled_convex_impl(const void* ssd, bool f16, const int64_t* argmin, const float* mesh, int h, int w, int d, int disp_hw, float* out,
-                             bool argmin_is_exact, void* workspace, size_t workspace_bytes, void* stream, const unsigned char* cmask) {
-    if (f16) return coupled_core(static_cast<const __half*>(ssd), argmin, mesh, h, w, d, disp_hw, out, argmin_is_exact, workspace, workspace_bytes, Prob2{0, 0, 0, 0}, 1, stream, false, cmask);
-    return coupled_core(static_cast<const float*>(ssd), argmin, mesh, h, w, d, disp_hw, out, argmin_is_exact, workspace, workspace_bytes, Prob2{0, 0, 0, 0}, 1, stream, false, cmask);
+                             void* workspace, size_t workspace_bytes, void* stream, const unsigned char* cmask) {
+    // the caller's `argmin` only seeds the first smoothing step (as in the reference): not vouched for
+    const CoupledPlan pl = coupled_plan(CoupledUse{h, w, d, disp_hw, f16, argmin != nullptr, false, cmask != nullptr, 1});
+    return with_volume_type(f16, ssd, [&](auto* p) { return coupled_core(pl, p, argmin, mesh, out, workspace, workspace_bytes, Prob2{0, 0, 0, 0}, stream, cmask); });
 }
 
 // Forward and reverse direction of a pair in the same launches (the per-pass kernels are latency-bound at 30 000 voxels, so two
-// problems cost about as much as one).  Both argmins must be the plain argmins of their volumes; both workspaces have the size
-// cvx_coupled_convex_workspace_bytes.  Falls back to two sequential solves when pruning is switched off.  argminA == argminB ==
-// nullptr: the plain argmin passes left their (cost, index) keys at the start of the respective workspace (launch_argmin_keys).
+// problems cost about as much as one), or one after the other where the plan says so.  Both workspaces have the size
+// cvx_coupled_convex_workspace_bytes; with seed Keys the plain argmin passes left their (cost, index) keys at the start of each.
 template <typename ST>
-static int coupled_dual_t(const ST* ssdA, const int64_t* argminA, float* outA, void* wsA, const ST* ssdB,
-                          const int64_t* argminB, float* outB, void* wsB, const float* mesh, int h, int w, int d, int disp_hw,
-                          size_t workspace_bytes, void* stream, bool counts_zeroed) {
-    const bool no_prune = options().no_prune != 0;
-    if (no_prune || !ssdB || !outB || !wsB) {
-        int rc = coupled_core(ssdA, argminA, mesh, h, w, d, disp_hw, outA, true, wsA, workspace_bytes, Prob2{0, 0, 0, 0}, 1, stream, counts_zeroed);
-        if (rc || !ssdB) return rc;
-        return coupled_core(ssdB, argminB, mesh, h, w, d, disp_hw, outB, true, wsB, workspace_bytes, Prob2{0, 0, 0, 0}, 1, stream, counts_zeroed);
+static int coupled_dual_t(const CoupledPlan& pl, const ST* ssdA, const int64_t* argminA, float* outA, void* wsA, const ST* ssdB,
+                          const int64_t* argminB, float* outB, void* wsB, const float* mesh, size_t workspace_bytes, void* stream) {
+    if (pl.nprob == 1) {
+        int rc = coupled_core(pl, ssdA, argminA, mesh, outA, wsA, workspace_bytes, Prob2{0, 0, 0, 0}, stream, nullptr);
+        if (rc || !pl.sequential) return rc;
+        return coupled_core(pl, ssdB, argminB, mesh, outB, wsB, workspace_bytes, Prob2{0, 0, 0, 0}, stream, nullptr);
     }
+    CVX_REQUIRE(ssdB && outB && wsB, "coupled_convex_dual: second problem missing");
     auto diff = [](const void* b, const void* a) { return (ptrdiff_t)(reinterpret_cast<uintptr_t>(b) - reinterpret_cast<uintptr_t>(a)); };
     // the carve-up of a workspace depends on its alignment modulo 256: equal residues give equal layouts
     if (((reinterpret_cast<uintptr_t>(wsA) ^ reinterpret_cast<uintptr_t>(wsB)) & 255) != 0)
         return fail(CVX_ERR_INVALID_ARG, "coupled_convex_dual: workspaces must share their alignment modulo 256");
     const Prob2 o{diff(ssdB, ssdA), diff(argminB, argminA), diff(outB, outA), diff(wsB, wsA)};
-    return coupled_core(ssdA, argminA, mesh, h, w, d, disp_hw, outA, true, wsA, workspace_bytes, o, 2, stream, counts_zeroed);
+    return coupled_core(pl, ssdA, argminA, mesh, outA, wsA, workspace_bytes, o, stream, nullptr);
 }
-int cvx::coupled_convex_dual_impl(const void* ssdA, const int64_t* argminA, float* outA, void* wsA, const void* ssdB, bool f16,
-                                  const int64_t* argminB, float* outB, void* wsB, const float* mesh, int h, int w, int d, int disp_hw,
-                                  size_t workspace_bytes, void* stream, bool counts_zeroed) {
-    if (f16) return coupled_dual_t(static_cast<const __half*>(ssdA), argminA, outA, wsA, static_cast<const __half*>(ssdB), argminB, outB, wsB, mesh, h, w, d, disp_hw, workspace_bytes, stream, counts_zeroed);
-    return coupled_dual_t(static_cast<const float*>(ssdA), argminA, outA, wsA, static_cast<const float*>(ssdB), argminB, outB, wsB, mesh, h, w, d, disp_hw, workspace_bytes, stream, counts_zeroed);
+int cvx::coupled_convex_dual_impl(const CoupledPlan& pl, const void* ssdA, const int64_t* argminA, float* outA, void* wsA, const void* ssdB,
+                                  const int64_t* argminB, float* outB, void* wsB, const float* mesh, size_t workspace_bytes, void* stream) {
+    return with_volume_type(pl.u.f16, ssdA, [&](auto* a) {
+        return coupled_dual_t(pl, a, argminA, outA, wsA, static_cast<decltype(a)>(ssdB), argminB, outB, wsB, mesh, workspace_bytes, stream);
+    });
 }
 
 // two ping-pong fields + the synchronisation words of k_ic_persistent

@@ -441,7 +441,7 @@ int launch_box_zero(const float* in, float* out, int C, int H, int W, int D, int
 int launch_smoother(const float* in, float* out, float* tmp, int C, int H, int W, int D, const cvx_smoother& sm, bool backward,
                     hipStream_t s);
 // (ssd: float32 cost volume, or half precision when f16 -- fp16 storage)
-int launch_argmin_keys(const void* ssd, bool f16, int K, size_t v, unsigned long long* keys, bool arm, hipStream_t s);   // arm = false: the caller set the keys to all ones
+int launch_argmin_keys(const void* ssd, bool f16, int K, size_t v, unsigned long long* keys, hipStream_t s);   // the caller set the keys to all ones (CoupledPrep::Keys)
 // the coupled-convex workspace: three key buffers, winners, minima, the pruned passes' work list and its two alternating lengths
 struct CoupledWs { unsigned long long* keys[3]; int* idx; float* smin; unsigned long long* list; int* counts; };
 CoupledWs coupled_layout(Carver& cv, int h, int w, int d, int disp_hw);
@@ -526,13 +526,37 @@ struct AdamRun {
 };
 int adam_run_impl(const AdamRun& r);
 size_t adam_record_floats(int C, size_t V);            // floats of one feature record of the Adam loop: [CP/4][V + 1][4], CP = C rounded up to 4
-// convex.hip: coupled convex regularisation behind cvx_coupled_convex_f32 (argmin_is_exact: see there)
+// convex.hip: HOW the coupled-convex stage runs -- decided once per call by coupled_plan (truth table there), read by the operators,
+// the whole-pair pipeline and certify.hip
+constexpr float kCoupledCoeffs[6] = {0.003f, 0.01f, 0.03f, 0.1f, 0.3f, 1.0f};   // torch.tensor([...]) float32 (convex_adam_utils.py:98)
+// the caller: geometry, half volume, int64 winners given (else the asker runs the plain argmin itself, in the form plan.prep names), vouched = they
+// are the plain argmin of this volume, a cell mask, one or two problems offered
+struct CoupledUse { int h, w, d, disp_hw; bool f16, winners, vouched, masked; int nprob; };
+enum class CoupledPasses { Pruned, Streamed };
+enum class CoupledSeed { Indices, Keys };                             // first smoothing step: int64 winners (narrowed to idx), or the keys in keys[0]
+enum class CoupledSmin { None, GatherAtSeed, FromKeys, OwnMinPass };  // per-voxel minimum of the pruned passes
+enum class CoupledPrep { CallerWinners, Keys, Winners64 };            // asker without winners: Keys = plain argmin into keys[0], which it set to all ones,
+                                                                      // both list lengths cleared; Winners64 = int64 winners (launch_argmin)
+enum class CoupledInvalid { No, MaskNeedsOwnMin, KeysNeedPruned };
+struct CoupledPlan {
+    CoupledUse u; CoupledInvalid invalid; CoupledPasses passes; CoupledSeed seed; CoupledSmin smin; CoupledPrep prep;
+    bool minkeys;                // keys[0] holds the library's own minimum pass and is handed to the pruned passes
+    int nprob; bool sequential;  // problems per launch; a two-problem request runs as two solves
+    int refine, stream_above;    // k_argmin_voxel / k_argmin_wave / k_cert_voxel arguments
+};
+CoupledPlan coupled_plan(const CoupledUse& u);
+// K-slices of a streaming argmin pass: about `target` workgroups, given xb workgroups along the voxels
+struct KSlices { int kslice, nslices; };
+static inline KSlices k_slices(int xb, int target, int K) {
+    const int want = cdiv(target, xb), kslice = cdiv(K, want > K ? K : (want < 1 ? 1 : want));
+    return {kslice, cdiv(K, kslice)};
+}
+// one problem, the caller's (unvouched) winners, optional cell mask [h][w][d] (the passes see ssd * cmask) / the plan's one or two problems (geometry
+// and element type: plan.u; argminA / argminB only where plan.seed == Indices)
 int coupled_convex_impl(const void* ssd, bool f16, const int64_t* argmin, const float* mesh, int h, int w, int d, int disp_hw, float* out,
-                        bool argmin_is_exact, void* workspace, size_t workspace_bytes, void* stream,
-                        const unsigned char* cmask = nullptr);   // cmask [h][w][d]: the passes see ssd * cmask (needs argmin_is_exact = false)
-int coupled_convex_dual_impl(const void* ssdA, const int64_t* argminA, float* outA, void* wsA, const void* ssdB, bool f16, const int64_t* argminB,
-                             float* outB, void* wsB, const float* mesh, int h, int w, int d, int disp_hw, size_t workspace_bytes,
-                             void* stream, bool counts_zeroed = false);   // counts_zeroed: the caller cleared CoupledWs::counts of both workspaces
+                        void* workspace, size_t workspace_bytes, void* stream, const unsigned char* cmask);
+int coupled_convex_dual_impl(const CoupledPlan& plan, const void* ssdA, const int64_t* argminA, float* outA, void* wsA, const void* ssdB,
+                             const int64_t* argminB, float* outB, void* wsB, const float* mesh, size_t workspace_bytes, void* stream);
 // (mind.hip's pooled descriptor and the plan of the MIND-SSC kernels: mind_common.h)
 // labelpool.hip: weighted one-hot label features delivered only through their stride poolings (g2 == 0 / out2 null: one pooling); no workspace
 int launch_label_pooled(const float* lab, int H, int W, int D, int C, const int* present, const float* weights, float mult, int g1, float* out1,
@@ -581,7 +605,7 @@ int corr_certified_argmin(const float* ssdu, const float* fix, const float* mov,
 // both directions (ssduB == nullptr: one) from the certified-fast volumes to the smoothed fields: plain argmin + six coupled passes
 int coupled_convex_cert_impl(const float* ssduA, const float* fixA, const float* movA, float* outA, void* wsA, const float* ssduB, const float* fixB,
                              const float* movB, float* outB, void* wsB, const float* mesh, int C, int h, int w, int d, int hw, size_t workspace_bytes,
-                             hipStream_t s, int stage = 0);      // stage 0 = everything, 1..5 = arm / stream A / stream B / certify the plain argmin / coupled passes
+                             int refine, hipStream_t s, int stage = 0);      // refine: CoupledPlan::refine; stage 0 = everything, 1..5 = arm / stream A / stream B / certify the plain argmin / coupled passes
 // boxmarch.hip: three chained 3^3 boxes (forward / adjoint / adjoint + Adam) for rows of at most 126 voxels
 bool box3_march_supported(int d);
 int launch_box3_march(const float* in, float* out, int h, int w, int d, bool backward, float* P, float* m, float* v,

@@ -323,11 +323,11 @@ struct PairRun {
     hipStream_t s;
     const float *featF, *featM;             // full-resolution features: the caller's, or the MIND descriptors where they are written
     const LabelPair* labels;                // label entry: the pooled one-hot features come straight from the two label maps
+    const CoupledPlan cp;                   // how the coupled-convex stage runs and what setup / plain_argmin prepare for it (made once per call, under the call's context)
     bool pooled_mind = false, mind_records = false;
     CoupledWs cw1{}, cw2{};                 // coupled-convex workspaces of the two directions (the plain argmin leaves its keys in their first key buffer)
 
     bool pooled() const { return pooled_mind || labels != nullptr; }      // fs / ms (and F2 / M2) are written by `features`
-    bool no_prune() const { return options().no_prune != 0; }        // streaming coupled passes need int64 winners
     bool f16() const { return p->fp16_storage != 0; }
     float* F(size_t off) const { return reinterpret_cast<float*>(ws + off); }
     int64_t* am() const { return reinterpret_cast<int64_t*>(ws + L.argmin); }
@@ -389,10 +389,11 @@ struct PairRun {
         const bool adam_tables = p->lambda_weight > 0;
         // (m, v zeroed here only if 16-byte stores fit: 3 * V2 floats from a 256-byte aligned offset)
         const bool zero_state = adam_tables && (3 * L.V2) % 4 == 0;
+        const bool clear_counts = cp.prep == CoupledPrep::Keys;      // (the keys are set to all ones whatever the plan says: DESIGN.md 34.1)
         PairSetup a = {{{L.h, L.w, L.d, L.h2, L.w2, L.d2},
                         {F(L.bh), F(L.bw), F(L.bd), adam_tables ? F(L.bh2) : nullptr, adam_tables ? F(L.bw2) : nullptr, adam_tables ? F(L.bd2) : nullptr}},
                        p->disp_hw, F(L.mesh), {cw1.keys[0], cw2.keys[0]}, L.v,
-                       {no_prune() ? nullptr : cw1.counts, no_prune() ? nullptr : cw2.counts},
+                       {clear_counts ? cw1.counts : nullptr, clear_counts ? cw2.counts : nullptr},
                        {zero_state ? reinterpret_cast<float4*>(ws + L.m) : nullptr, zero_state ? reinterpret_cast<float4*>(ws + L.v_) : nullptr}, 3 * L.V2 / 4};
         hipLaunchKernelGGL(k_pair_setup, dim3(zero_state ? 1024 : 64), dim3(256), 0, s, a);
         if (adam_tables && !zero_state) {
@@ -401,8 +402,8 @@ struct PairRun {
         }
     }
     int plain_argmin(const float* ssd, unsigned long long* keys, int64_t* argmin, const char* done) {     // keys stay in the coupled workspace's first buffer
-        const int rc = no_prune() ? launch_argmin(ssd, f16(), nullptr, nullptr, 0.0f, false, L.K, L.v, keys, argmin, s)
-                                : launch_argmin_keys(ssd, f16(), L.K, L.v, keys, /*arm=*/false, s);
+        const int rc = cp.prep == CoupledPrep::Winners64 ? launch_argmin(ssd, f16(), nullptr, nullptr, 0.0f, false, L.K, L.v, keys, argmin, s)
+                                                         : launch_argmin_keys(ssd, f16(), L.K, L.v, keys, s);     // prep Keys: `setup` armed them
         if (rc == CVX_OK) mark(done, s);
         return rc;
     }
@@ -427,12 +428,12 @@ struct PairRun {
         // argmin decision certified against the exact arithmetic or evaluated exactly (certify.hip) -- the SAME winners, hence the same field bits,
         // as the exact kernels below; packaged operator only (SSD, two boxes, float32, pruned passes).
         // (which geometries take it, and with which kernel: corr_plan, correlate.hip)
-        const CorrPlan plan = corr_plan(L.C, L.h, L.w, L.d, p->disp_hw, CorrUse{variant, p->ic != 0, no_prune()});
+        const CorrPlan plan = corr_plan(L.C, L.h, L.w, L.d, p->disp_hw, CorrUse{variant, p->ic != 0, cp.passes == CoupledPasses::Streamed});
         if (plan.pair_cert) {
             const size_t fws = corr_certfast_workspace_bytes(L.C, L.h, L.w, L.d, p->disp_hw), qws = corr_certify_workspace_bytes(L.C, L.h, L.w, L.d, p->disp_hw);
             auto cert_stage = [&](int stage) {
                 return coupled_convex_cert_impl(F(L.ssd), F(L.fs), F(L.ms), F(L.soft), ws + L.cert_ws, p->ic ? F(L.ssd2) : nullptr, F(L.ms), F(L.fs),
-                                                p->ic ? F(L.soft2) : nullptr, p->ic ? ws + L.cert_ws2 : nullptr, F(L.mesh), L.C, L.h, L.w, L.d, p->disp_hw, qws, s, stage);
+                                                p->ic ? F(L.soft2) : nullptr, p->ic ? ws + L.cert_ws2 : nullptr, F(L.mesh), L.C, L.h, L.w, L.d, p->disp_hw, qws, cp.refine, s, stage);
             };
             if ((rc = cert_stage(1))) return rc;                                    // keys, counters, tail values
             if ((rc = launch_corr_certfast(F(L.fs), F(L.ms), L.C, L.h, L.w, L.d, p->disp_hw, F(L.ssd), ws + L.corr_ws, fws, s))) return rc;
@@ -463,9 +464,10 @@ struct PairRun {
             if (p->ic && (rc = exact_direction(F(L.ms), F(L.fs), variant ? &copt : nullptr, F(L.ssd2), cw2.keys[0], am2(), "correlate_rev", "argmin_rev"))) return rc;
         }
         // both coupled-convex solves in the same launches (ic) or the forward one alone
-        return coupled_convex_dual_impl(F(L.ssd), no_prune() ? am() : nullptr, F(L.soft), ws + L.conv_ws, p->ic ? F(L.ssd2) : nullptr, f16(), no_prune() ? am2() : nullptr,
-                                        p->ic ? F(L.soft2) : nullptr, p->ic ? ws + L.conv_ws2 : nullptr, F(L.mesh), L.h, L.w, L.d,
-                                        p->disp_hw, cvx_coupled_convex_workspace_bytes(L.h, L.w, L.d, p->disp_hw), s, /*counts_zeroed=*/!no_prune());
+        const bool idx = cp.seed == CoupledSeed::Indices;
+        return coupled_convex_dual_impl(cp, F(L.ssd), idx ? am() : nullptr, F(L.soft), ws + L.conv_ws, p->ic ? F(L.ssd2) : nullptr, idx ? am2() : nullptr,
+                                        p->ic ? F(L.soft2) : nullptr, p->ic ? ws + L.conv_ws2 : nullptr, F(L.mesh),
+                                        cvx_coupled_convex_workspace_bytes(L.h, L.w, L.d, p->disp_hw), s);
     }
     // dst = interpolate(src * grid_sp_adam, (H,W,D)) of an Adam-grid field (:182), then k > 0: three zero-padded k^3 box filters (:185-191)
     int upsample_smoothed(const float* src, int k, float* dst) {
@@ -536,7 +538,9 @@ static int register_pair_core(const float* img_fixed, const float* img_moving, c
     corr_fused_set_prep_hook(g_profiling ? +[](hipStream_t st) { mark("correlate_prep", st); } : nullptr);
     struct HookReset { ~HookReset() { corr_fused_set_prep_hook(nullptr); } } hook_reset;
 
-    PairRun run = {p, L, static_cast<char*>(workspace), s, feat_fixed, feat_moving, labels};
+    // no winners, vouched: the run computes the plain argmin itself, as keys or as int64 winners (cp.prep); made here, under `scope`, and never kept
+    PairRun run = {p, L, static_cast<char*>(workspace), s, feat_fixed, feat_moving, labels,
+                   coupled_plan(CoupledUse{L.h, L.w, L.d, p->disp_hw, p->fp16_storage != 0, false, true, false, p->ic ? 2 : 1})};
     const bool adam = p->lambda_weight > 0;
     if ((rc = run.features(img_fixed, img_moving))) return rc;
     run.setup();
@@ -745,8 +749,7 @@ extern "C" int cvx_convex_stage_f32(const float* feat_fix, const float* feat_mov
     auto direction = [&](const float* a, const float* b, const unsigned char* mask, float* soft) -> int {
         int r = cvx_correlate_ex_f32(a, b, p->C, h, w, d, p->disp_hw, nullptr, L.ssd, L.argmin, L.corr_ws, L.corr_bytes, stream);
         if (r) return r;
-        return coupled_convex_impl(L.ssd, false, L.argmin, L.mesh, h, w, d, p->disp_hw, soft, /*argmin_is_exact=*/false, L.conv_ws, L.conv_bytes,
-                                   stream, mask);
+        return coupled_convex_impl(L.ssd, false, L.argmin, L.mesh, h, w, d, p->disp_hw, soft, L.conv_ws, L.conv_bytes, stream, mask);
     };
     if (p->ic_iters == 0) {                     // (:335-341) forward direction only
         float* soft = coarse_field ? coarse_field : L.soft;
