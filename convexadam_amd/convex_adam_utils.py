@@ -502,3 +502,6 @@ from .prep import (compute_steps_for_sliding_window, create_nonzero_mask, crop_t
                    nnUNetCTnorm, nnUNetNorm, nnUNetNormProps, normalise_and_crop, pdist_squared)
 # the opposite direction of a result -- inverse and composition of displacement fields (no counterpart in the reference): csrc/fieldops.hip
 from .fieldops import apply_convex_inverse, compose_fields, invert_field  # noqa: E402,F401
+# the affine model: least-trimmed affine fit, the affine as a field, affine pre-alignment (l2r_2020_convexAdam_CuRIOUS.py:272-278): csrc/affine.hip
+from .affine import (affine_from_field, affine_to_field, convex_adam_affine, find_affine_3d, least_trimmed_affine,  # noqa: E402,F401
+                     least_trimmed_squares, register_with_affine)

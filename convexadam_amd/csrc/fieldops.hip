@@ -152,14 +152,6 @@ static void launch_compose_out(const ComposeArgs& c, bool o64, hipStream_t s) {
     else launch_compose<TA, TB, float>(c, s);
 }
 
-// a field operand: the strides do not fold components onto each other (the rule of cvx_field_to_grid_f64) and the base is aligned
-static bool field_strides_ok(int64_t cs, int64_t vs, size_t V) {
-    const bool range = cs > 0 && vs > 0 && cs < ((int64_t)1 << 40) && vs < ((int64_t)1 << 20);
-    return range && (vs >= 3 * cs || cs >= (int64_t)V * vs);
-}
-static size_t field_bytes(int64_t cs, int64_t vs, size_t V, int f64) { return (size_t)(2 * cs + (int64_t)(V - 1) * vs + 1) * (f64 ? 8 : 4); }
-static bool field_aligned(const void* p, int f64) { return ((uintptr_t)p & (f64 ? 7 : 3)) == 0; }
-
 }  // namespace cvx
 
 using namespace cvx;

@@ -1,5 +1,6 @@
-// geometry_args.h -- the host-side argument checks shared by the entry points of geometry.hip and fieldmean.hip: one statement of what an
-// overlap, a finite host array, an acceptable volume and an index map are.  Included after cvx_common.h and interp_f64.h.
+// geometry_args.h -- the host-side argument checks shared by the entry points of geometry.hip, fieldmean.hip, fieldops.hip and
+// affine.hip: one statement of what an overlap, a finite host array, an acceptable volume, a field operand and an index map are.
+// Included after cvx_common.h and interp_f64.h.
 #pragma once
 #include <limits.h>
 #include <math.h>
@@ -25,6 +26,14 @@ static size_t voxels(int a, int b, int c) {
     if (v > (uint64_t)INT_MAX) return 0;
     return (size_t)v;
 }
+// a field operand (include/convexadam_field.h, convexadam_affine.h): the strides do not fold components onto each other (the rule of
+// cvx_field_to_grid_f64), the bytes it spans, and the base aligned to its element
+static bool field_strides_ok(int64_t cs, int64_t vs, size_t V) {
+    const bool range = cs > 0 && vs > 0 && cs < ((int64_t)1 << 40) && vs < ((int64_t)1 << 20);
+    return range && (vs >= 3 * cs || cs >= (int64_t)V * vs);
+}
+static size_t field_bytes(int64_t cs, int64_t vs, size_t V, int f64) { return (size_t)(2 * cs + (int64_t)(V - 1) * vs + 1) * (f64 ? 8 : 4); }
+static bool field_aligned(const void* p, int f64) { return ((uintptr_t)p & (f64 ? 7 : 3)) == 0; }
 static IndexMap make_map(const double* map12) {
     IndexMap g;
     for (int i = 0; i < 9; ++i) g.m[i] = map12[i];

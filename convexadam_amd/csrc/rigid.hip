@@ -17,6 +17,7 @@
 //                spent on it, otherwise an ordered ballot scan writes the set as a byte mask.
 //           Every global word a thread reads back (patterns, set mask, inlier mask) is one it wrote itself: the strided walk gives
 //           point i to thread i % 1024 in every pass, so the passes need nothing beyond the workgroup barriers between them.
+//           The workgroup sum, the residual pattern and the selection live in lts_common.h, shared with the affine fit (affine.hip).
 //           A non-finite centroid or covariance (a non-finite coordinate among the points a fit uses; the reference's torch.svd raises
 //           on it) stops the kernel before T or the inlier mask is written and leaves status = 1, which the host reads back.
 //   warp    k_affine_warp: F.grid_sample(vol, F.affine_grid(theta, (1,C,ho,wo,do), align_corners=False), mode, zeros, False) with the
@@ -27,54 +28,11 @@
 //           nearbyint).  theta lives in device memory, so a fitted T feeds the warp without a host round trip; the C channels share
 //           one coordinate computation.
 #include "cvx_common.h"
+#include "lts_common.h"
 
 namespace cvx {
 
-constexpr int LTS_THREADS = 1024;
-constexpr int LTS_WAVES = LTS_THREADS / 64;
-constexpr int64_t LTS_MAX_N = (int64_t)1 << 28;
-
-// ---- least-trimmed rigid fit -------------------------------------------------------------------------------------------------------
-// Workgroup sum of M doubles in a fixed order; every thread gets the M totals in out[] (LDS).
-template <int M>
-__device__ __forceinline__ void wg_sum(double (&v)[M], double* red, double* out) {
-    for (int off = 32; off >= 1; off >>= 1)
-        for (int m = 0; m < M; ++m) v[m] += __shfl_xor(v[m], off);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0)
-        for (int m = 0; m < M; ++m) red[wave * M + m] = v[m];
-    cvx_barrier();
-    if (threadIdx.x < M) {
-        double s = red[threadIdx.x];
-        for (int w2 = 1; w2 < LTS_WAVES; ++w2) s += red[w2 * M + threadIdx.x];
-        out[threadIdx.x] = s;
-    }
-    cvx_barrier();
-}
-
-// The bin b of an LDS histogram (nbins = LTS_THREADS * PER) with cum(< b) < k <= cum(<= b), 1 <= k <= total: res[0] = b,
-// res[1] = cum(< b).  Ends with a barrier.
-template <int PER>
-__device__ __forceinline__ void find_bin(const unsigned* hist, unsigned k, unsigned* wsum, unsigned* res) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    unsigned c[PER], local = 0;
-    for (int j = 0; j < PER; ++j) { c[j] = hist[tid * PER + j]; local += c[j]; }
-    unsigned x = local;
-    for (int off = 1; off < 64; off <<= 1) {
-        const unsigned y = __shfl_up(x, off);
-        if (lane >= off) x += y;
-    }
-    if (lane == 63) wsum[wave] = x;
-    cvx_barrier();
-    unsigned cum = x - local;
-    for (int w2 = 0; w2 < wave; ++w2) cum += wsum[w2];
-    for (int j = 0; j < PER; ++j) {
-        if (cum < k && k <= cum + c[j]) { res[0] = (unsigned)(tid * PER + j); res[1] = cum; }
-        cum += c[j];
-    }
-    cvx_barrier();
-}
-
+// ---- least-trimmed rigid fit (workgroup sum, residual pattern and selection: lts_common.h) ---------------------------------------------
 // Eigen-decomposition of a symmetric 4x4 matrix by cyclic Jacobi rotations (A is diagonalised in place, V gets the eigenvectors).
 __device__ void jacobi4(double A[4][4], double V[4][4]) {
     for (int p = 0; p < 4; ++p)
@@ -141,35 +99,13 @@ __device__ void horn_rotation(const double S[9], const double xm[3], const doubl
     }
 }
 
-__device__ __forceinline__ unsigned residual_bits(const float* __restrict__ f, const float* __restrict__ m, const float* T12) {
-    const float f0 = f[0], f1 = f[1], f2 = f[2], f3 = f[3];
-    float s = 0.0f;
-    for (int a = 0; a < 3; ++a) {
-        float p = f0 * T12[4 * a];
-        p = fmaf(f1, T12[4 * a + 1], p);
-        p = fmaf(f2, T12[4 * a + 2], p);
-        p = fmaf(f3, T12[4 * a + 3], p);
-        const float e = m[a] - p;
-        s = s + e * e;
-    }
-    const float e3 = m[3] - f3;                       // row 3 of T is (0, 0, 0, 1)
-    s = s + e3 * e3;
-    const float r = sqrtf(s);
-    return r != r ? 0x7fffffffu : __float_as_uint(r);
-}
-
-// mode 0: every point; 1: pattern <= thr; 2: the byte mask
-__device__ __forceinline__ bool in_set(int mode, int i, const unsigned* rbits, const unsigned char* sel, unsigned thr) {
-    return mode == 0 ? true : (mode == 1 ? rbits[i] <= thr : sel[i] != 0);
-}
-
 __global__ __launch_bounds__(LTS_THREADS) void k_rigid_lts(const float* __restrict__ fixed, int ldf, const float* __restrict__ moving, int ldm,
                                                            int n, int iters, float* __restrict__ T, unsigned char* __restrict__ inliers,
                                                            unsigned* rbits, unsigned char* sel, int* __restrict__ status) {
     __shared__ double red[LTS_WAVES * 9], tot[9];
-    __shared__ unsigned hist[2048], wsum[LTS_WAVES], res[2];
+    __shared__ LtsSelectLds lds;
     __shared__ float T12[12];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int K = n / 2;
     int mode = 0, bad = 0;
     unsigned thr = 0;
@@ -207,63 +143,10 @@ __global__ __launch_bounds__(LTS_THREADS) void k_rigid_lts(const float* __restri
         cvx_barrier();
         if (it == iters - 1) break;
 
-        // residuals + radix select of the K-th smallest pattern
+        // residuals + selection of the K points with the smallest patterns
         float Tl[12];
         for (int k = 0; k < 12; ++k) Tl[k] = T12[k];
-        for (int j = tid; j < 2048; j += LTS_THREADS) hist[j] = 0u;
-        cvx_barrier();
-        for (int i = tid; i < n; i += LTS_THREADS) {
-            const unsigned b = residual_bits(fixed + (size_t)i * 4, moving + (size_t)i * 4, Tl);
-            rbits[i] = b;
-            atomicAdd(&hist[b >> 21], 1u);
-        }
-        cvx_barrier();
-        find_bin<2>(hist, (unsigned)K, wsum, res);
-        const unsigned b1 = res[0], below1 = res[1];
-        for (int j = tid; j < 2048; j += LTS_THREADS) hist[j] = 0u;
-        cvx_barrier();
-        for (int i = tid; i < n; i += LTS_THREADS) {
-            const unsigned b = rbits[i];
-            if ((b >> 21) == b1) atomicAdd(&hist[(b >> 10) & 0x7ffu], 1u);
-        }
-        cvx_barrier();
-        find_bin<2>(hist, (unsigned)K - below1, wsum, res);
-        const unsigned pre = (b1 << 11) | res[0], below2 = res[1];
-        for (int j = tid; j < 1024; j += LTS_THREADS) hist[j] = 0u;
-        cvx_barrier();
-        for (int i = tid; i < n; i += LTS_THREADS) {
-            const unsigned b = rbits[i];
-            if ((b >> 10) == pre) atomicAdd(&hist[b & 0x3ffu], 1u);
-        }
-        cvx_barrier();
-        find_bin<1>(hist, (unsigned)K - below1 - below2, wsum, res);
-        thr = (pre << 10) | res[0];
-        const unsigned need = (unsigned)K - below1 - below2 - res[1], eq = hist[res[0]];
-        cvx_barrier();                                                          // hist / res are rewritten by the next fit
-        if (eq == need) {
-            mode = 1;
-            continue;
-        }
-        // ties at the threshold: the lowest-index `need` of them, by an ordered scan over chunks of LTS_THREADS points
-        unsigned run = 0;
-        for (int base = 0; base < n; base += LTS_THREADS) {
-            const int i = base + tid;
-            const unsigned b = i < n ? rbits[i] : 0xffffffffu;
-            const bool e = b == thr;
-            const unsigned long long bal = __ballot(e);
-            const unsigned before = (unsigned)__popcll(bal & ((1ull << lane) - 1ull));
-            if (lane == 0) wsum[wave] = (unsigned)__popcll(bal);
-            cvx_barrier();
-            unsigned wb = 0, all = 0;
-            for (int w2 = 0; w2 < LTS_WAVES; ++w2) {
-                if (w2 < wave) wb += wsum[w2];
-                all += wsum[w2];
-            }
-            if (i < n) sel[i] = (unsigned char)(b < thr || (e && run + wb + before < need));
-            run += all;
-            cvx_barrier();
-        }
-        mode = 2;
+        mode = lts_select(n, K, rbits, sel, lds, thr, [&](int i) { return residual_bits<true>(fixed + (size_t)i * 4, moving + (size_t)i * 4, Tl); });
     }
     if (!bad) {
         if (tid < 16) T[tid] = tid < 12 ? T12[tid] : (tid == 15 ? 1.0f : 0.0f);
@@ -314,9 +197,6 @@ __global__ __launch_bounds__(256) void k_affine_warp(const float* __restrict__ v
 
 using namespace cvx;
 
-// residual bits, inlier selection, the status word
-struct LtsWs { unsigned* rbits; unsigned char* sel; int* status; };
-static LtsWs lts_layout(Carver& cv, int64_t n) { return LtsWs{cv.take<unsigned>((size_t)n), cv.take<unsigned char>((size_t)n), cv.take<int>(1)}; }
 extern "C" size_t cvx_rigid_lts_workspace_bytes(int64_t n) {
     if (n < 2 || n > LTS_MAX_N) return 0;
     Carver m; lts_layout(m, n); return align_up(m.used, 256);          // (no slack: the status word rounded to its granule, as this query always was)
