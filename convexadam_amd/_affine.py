@@ -1,10 +1,10 @@
 """ctypes binding of the affine model (include/convexadam_affine.h) onto the handle _lib.lib() returns.
 
-A table of its own, as _prep.py and _field.py have: _lib.SIGNATURES mirrors include/convexadam_hip.h name for name, AFFINE_SIGNATURES mirrors
+A table of its own, as _prep.py and _field.py have, typed by _lib.bind: _lib.SIGNATURES mirrors include/convexadam_hip.h name for name, AFFINE_SIGNATURES mirrors
 include/convexadam_affine.h the same way (tests/test_affine_abi.py).  All headers describe the one libconvexadam_hip.so; CVX_ABI_VERSION is
 unchanged."""
 import ctypes as C
-import threading
+import functools
 
 from . import _lib
 
@@ -18,20 +18,8 @@ AFFINE_SIGNATURES = {
     "cvx_affine_field_f64": (_i, [_vp, _i, _i, _i] + _FIELD + _FIELD + [_vp]),
 }
 
-_bound = None
-_lock = threading.Lock()
 
-
+@functools.lru_cache(maxsize=None)
 def lib():
     """The library handle of _lib.lib() with the affine entry points typed (raises if one is missing: there is no fallback)."""
-    global _bound
-    if _bound is None:
-        with _lock:
-            if _bound is None:
-                L = _lib.lib()
-                for name, (res, args) in AFFINE_SIGNATURES.items():
-                    fn = getattr(L, name)
-                    fn.restype = res
-                    fn.argtypes = args
-                _bound = L
-    return _bound
+    return _lib.bind(_lib.lib(), AFFINE_SIGNATURES)

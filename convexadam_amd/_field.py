@@ -1,10 +1,10 @@
 """ctypes binding of the displacement-field operators (include/convexadam_field.h) onto the handle _lib.lib() returns.
 
-A table of its own, as _prep.py has: _lib.SIGNATURES mirrors include/convexadam_hip.h name for name, FIELD_SIGNATURES mirrors
+A table of its own, as _prep.py has, typed by _lib.bind: _lib.SIGNATURES mirrors include/convexadam_hip.h name for name, FIELD_SIGNATURES mirrors
 include/convexadam_field.h the same way (tests/test_fieldops_abi.py).  All headers describe the one libconvexadam_hip.so;
 CVX_ABI_VERSION is unchanged."""
 import ctypes as C
-import threading
+import functools
 
 from . import _lib
 
@@ -17,20 +17,8 @@ FIELD_SIGNATURES = {
     "cvx_field_compose_f64": (_i, _FIELD + _FIELD + [_i, _i, _i] + _FIELD + [_vp]),
 }
 
-_bound = None
-_lock = threading.Lock()
 
-
+@functools.lru_cache(maxsize=None)
 def lib():
     """The library handle of _lib.lib() with the field operators typed (raises if one is missing: there is no fallback)."""
-    global _bound
-    if _bound is None:
-        with _lock:
-            if _bound is None:
-                L = _lib.lib()
-                for name, (res, args) in FIELD_SIGNATURES.items():
-                    fn = getattr(L, name)
-                    fn.restype = res
-                    fn.argtypes = args
-                _bound = L
-    return _bound
+    return _lib.bind(_lib.lib(), FIELD_SIGNATURES)

@@ -179,6 +179,16 @@ _lib = None
 _lock = threading.Lock()
 
 
+def bind(L, table):
+    """Types the entry points of a name -> (restype, argtypes) table on the handle L (raises if one is missing: there is no fallback).
+    Setting the same types twice is harmless, so the cached lib() of _prep.py, _field.py and _affine.py need no lock."""
+    for name, (res, args) in table.items():
+        fn = getattr(L, name)
+        fn.restype = res
+        fn.argtypes = args
+    return L
+
+
 def lib():
     """Loads the HIP library (raises if it has not been built -- never falls back)."""
     global _lib
@@ -188,11 +198,7 @@ def lib():
                 if not os.path.exists(LIB_PATH):
                     raise RuntimeError("%s not found: build it with `python -m convexadam_amd.csrc.build` "
                                        "(there is no CPU fallback)" % LIB_PATH)
-                L = C.CDLL(LIB_PATH)
-                for name, (res, args) in SIGNATURES.items():
-                    fn = getattr(L, name)
-                    fn.restype = res
-                    fn.argtypes = args
+                L = bind(C.CDLL(LIB_PATH), SIGNATURES)
                 if L.cvx_version() != ABI_VERSION:
                     raise RuntimeError("%s reports ABI version %d, this binding needs %d (struct layouts differ): rebuild with "
                                        "`python -m convexadam_amd.csrc.build`" % (LIB_PATH, L.cvx_version(), ABI_VERSION))
@@ -214,9 +220,62 @@ def require_device_tensor(t, name):
     return t
 
 
+def _shape(t, name):
+    """The shape of a tensor, read from its metadata only (the callers' checks answer before any device is touched)."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("%s must be a torch.Tensor" % name)
+    return tuple(int(s) for s in t.shape)
+
+
 def f32c(t):
     """float32, contiguous view/copy of a device tensor."""
     return t.detach().to(torch.float32).contiguous()
+
+
+def field_operand(t, grid=None, name="field", strict=False, planar=None, f32=False):
+    """A displacement field as the kernels read it (a field operand of include/convexadam_field.h) ->
+    (contiguous tensor, (H, W, D), component stride, voxel stride, is_f64), strides in elements.
+
+    t       (H, W, D, 3) or (3, H, W, D) tensor; float32 and float64 are read as they are, every other dtype as float64 (f32=True: all as
+            float32, cropfield's rule)
+    grid    the (H, W, D) the field must live on; None reads it from the shape, where (3, 3, 3, 3) is (H, W, D, 3), what convex_adam_pt
+            returns -- or, with strict=True, is refused like every shape that does not say which layout it is
+    planar  True / False: the caller knows the layout to be (3, H, W, D) / (H, W, D, 3); None: the shape says, (H, W, D, 3) first"""
+    t = t.detach()
+    s = tuple(int(n) for n in t.shape)
+    if len(s) != 4 and (grid is None or strict):
+        raise ValueError("%s must be (H, W, D, 3) or (3, H, W, D), got %s" % (name, s))
+    if grid is None:
+        if s[0] != 3 and s[-1] != 3 and not strict:
+            raise ValueError("%s must be (H, W, D, 3) or (3, H, W, D), got %s" % (name, s))
+        if strict and (s[0] == 3) == (s[-1] == 3):
+            raise ValueError("a field of shape %s does not say which of its layouts it is: pass field_grid" % (s,))
+        grid = s[:3] if s[-1] == 3 else s[1:]
+    grid = tuple(int(n) for n in grid)
+    if s == grid + (3,) and not planar:
+        cs, vs = 1, 3
+    elif s == (3,) + grid and planar is not False:
+        cs, vs = grid[0] * grid[1] * grid[2], 1
+    else:
+        raise ValueError("field must be (H, W, D, 3) or (3, H, W, D) on the grid (z, y, x) = %s, got %s" % (grid, s))
+    if f32:
+        t = t.to(torch.float32)
+    elif t.dtype not in (torch.float32, torch.float64):
+        t = t.to(torch.float64)                                  # integers (and half floats) are computed in float64
+    return t.contiguous(), grid, cs, vs, int(t.dtype == torch.float64)
+
+
+def field_operand_from(f, name, device):
+    """field_operand of a device tensor (read in place), or of an (H, W, D, 3) array, image or host tensor uploaded to `device` (None: the
+    current one) as float64 -> field_operand's tuple + (came from the host,)"""
+    if isinstance(f, torch.Tensor) and f.is_cuda:
+        return field_operand(f, name=name) + (False,)
+    from .convex_adam_utils import validate_image          # (at call time: convex_adam_utils imports this module)
+    t = validate_image(f)
+    if t.dim() != 4 or t.shape[-1] != 3:
+        raise ValueError("%s must be (H, W, D, 3), got %s" % (name, tuple(t.shape)))
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    return field_operand(t.to(dev, torch.float64), name=name) + (True,)
 
 
 def ptr(t):

@@ -1,9 +1,10 @@
 """ctypes binding of the preprocessing entry points (include/convexadam_prep.h) onto the handle _lib.lib() returns.
 
-A table of its own: _lib.SIGNATURES mirrors include/convexadam_hip.h name for name, PREP_SIGNATURES mirrors include/convexadam_prep.h the
-same way (tests/test_prep_abi.py).  Both headers describe the one libconvexadam_hip.so; CVX_ABI_VERSION is unchanged."""
+A table of its own, typed by _lib.bind: _lib.SIGNATURES mirrors include/convexadam_hip.h name for name, PREP_SIGNATURES mirrors
+include/convexadam_prep.h the same way (tests/test_prep_abi.py).  Both headers describe the one libconvexadam_hip.so; CVX_ABI_VERSION is
+unchanged."""
 import ctypes as C
-import threading
+import functools
 
 from . import _lib
 
@@ -21,20 +22,8 @@ PREP_SIGNATURES = {
     "cvx_prep_mask_bbox_i32": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
 }
 
-_bound = None
-_lock = threading.Lock()
 
-
+@functools.lru_cache(maxsize=None)
 def lib():
     """The library handle of _lib.lib() with the preprocessing entry points typed (raises if one is missing: there is no fallback)."""
-    global _bound
-    if _bound is None:
-        with _lock:
-            if _bound is None:
-                L = _lib.lib()
-                for name, (res, args) in PREP_SIGNATURES.items():
-                    fn = getattr(L, name)
-                    fn.restype = res
-                    fn.argtypes = args
-                _bound = L
-    return _bound
+    return _lib.bind(_lib.lib(), PREP_SIGNATURES)

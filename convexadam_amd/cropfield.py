@@ -18,7 +18,7 @@ from collections import namedtuple
 import numpy as np
 import torch
 
-from ._lib import check, f32c, lib, ptr, require_device_tensor, stream_ptr
+from ._lib import _shape, check, f32c, field_operand, lib, ptr, require_device_tensor, stream_ptr
 
 CROP_FIELD_VOXELS, CROP_OUT_F32, CROP_IDENTITY = 1, 2, 4          # the flags of cvx_crop_field_half_f32
 _FLIP_BITS = {"x": 1, "y": 2, "z": 4}                              # the reference's letters: 'x' = array axis 0, 'y' = 1, 'z' = 2
@@ -115,13 +115,6 @@ def read_cases(path, ref_spacing=2.0, flip="xy"):
     return cases
 
 
-def _shape(t, name):
-    """The shape of a tensor, read from its metadata only (the checks below answer before any device is touched)."""
-    if not isinstance(t, torch.Tensor):
-        raise TypeError("%s must be a torch.Tensor" % name)
-    return tuple(int(s) for s in t.shape)
-
-
 def _spacing(v, name):
     try:
         s = tuple(float(x) for x in (v.tolist() if isinstance(v, torch.Tensor) else v))
@@ -143,7 +136,10 @@ def _check_full(full):
         raise ValueError("an original grid of %s has no half-resolution output" % (tuple(full),))
 
 
-def _launch(f, cs, vs, grid, geom, full, flip_mask, flags, out_dtype):
+def _launch(t, name, planar, grid, geom, full, flip_mask, flags, out_dtype):
+    """t: the field with its leading 1 (if any), float32 to the kernel whatever its dtype; planar: (3, H, W, D), else (H, W, D, 3)"""
+    t = require_device_tensor(t, name)
+    f, grid, cs, vs, _ = field_operand(t.reshape(t.shape[-4:]), grid, planar=planar, f32=True)
     out = torch.empty((3,) + tuple(s // 2 for s in full), dtype=out_dtype, device=f.device)
     g = (C.c_double * 27)(*geom.tolist()) if geom is not None else None
     with torch.cuda.device(f.device):
@@ -179,8 +175,7 @@ def convert_crop_field(case, fix_affine_disp_p, out_dtype=torch.float16):
     case.check_field_shape(s[1:4])
     _check_full(case.fix_shape)
     flags = _out_flag(out_dtype)
-    f = f32c(require_device_tensor(fix_affine_disp_p, "fix_affine_disp_p"))
-    return _launch(f, 1, 3, s[1:4], case.geometry(), case.fix_shape, case.flip_mask, flags, out_dtype)
+    return _launch(fix_affine_disp_p, "fix_affine_disp_p", False, s[1:4], case.geometry(), case.fix_shape, case.flip_mask, flags, out_dtype)
 
 
 def submission_field(disp_voxels, pre_fix_spacing, pre_mov_spacing, case, out_dtype=torch.float16):
@@ -198,8 +193,7 @@ def submission_field(disp_voxels, pre_fix_spacing, pre_mov_spacing, case, out_dt
     _check_full(case.fix_shape)
     geom = case.geometry(_spacing(pre_fix_spacing, "pre_fix_spacing"), _spacing(pre_mov_spacing, "pre_mov_spacing"))
     flags = _out_flag(out_dtype) | CROP_FIELD_VOXELS
-    f = f32c(require_device_tensor(disp_voxels, "disp_voxels"))
-    return _launch(f, s[2] * s[3] * s[4], 1, s[2:], geom, case.fix_shape, case.flip_mask, flags, out_dtype)
+    return _launch(disp_voxels, "disp_voxels", True, s[2:], geom, case.fix_shape, case.flip_mask, flags, out_dtype)
 
 
 def half_resolution_field(disp, out_dtype=torch.float32):
@@ -212,6 +206,5 @@ def half_resolution_field(disp, out_dtype=torch.float32):
         raise ValueError("disp must be (1, 3, H, W, D) or (3, H, W, D), got %s" % (s,))
     _check_full(s[-3:])
     flags = _out_flag(out_dtype) | CROP_IDENTITY
-    f = f32c(require_device_tensor(disp, "disp"))
-    out = _launch(f, s[-3] * s[-2] * s[-1], 1, s[-3:], None, s[-3:], 0, flags, out_dtype)
+    out = _launch(disp, "disp", True, s[-3:], None, s[-3:], 0, flags, out_dtype)
     return out.unsqueeze(0) if lead else out

@@ -144,10 +144,10 @@ extern "C" int cvx_affine_lts_f32(const float* fixed, int ld_fixed, const float*
                 AFFINE_MAX_LD);
     CVX_REQUIRE(field_aligned(fixed, 0) && field_aligned(moving, 0) && field_aligned(X, 0), "cvx_affine_lts_f32: a buffer is not aligned to 4 bytes");
     const size_t fb = ((size_t)(n - 1) * ld_fixed + (ld_fixed >= 4 ? 4 : 3)) * 4, mb = ((size_t)(n - 1) * ld_moving + (ld_moving >= 4 ? 4 : 3)) * 4;
-    CVX_REQUIRE(!ranges_overlap(X, 64, fixed, fb) && !ranges_overlap(X, 64, moving, mb), "cvx_affine_lts_f32: X overlaps the points");
-    CVX_REQUIRE(!inliers || (!ranges_overlap(inliers, (size_t)n, fixed, fb) && !ranges_overlap(inliers, (size_t)n, moving, mb) &&
-                             !ranges_overlap(inliers, (size_t)n, X, 64)),
-                "cvx_affine_lts_f32: inliers overlaps the points or X");
+    const Span ins[2] = {{fixed, fb}, {moving, mb}}, outs[2] = {{X, 64}, {inliers, (size_t)n}};
+    const Overlaps ov = find_overlaps(outs, ins);
+    CVX_REQUIRE(ov.out != 0, "cvx_affine_lts_f32: X overlaps the points");
+    CVX_REQUIRE(ov.out < 0 && ov.a < 0, "cvx_affine_lts_f32: inliers overlaps the points or X");
     const size_t need = cvx_affine_lts_workspace_bytes(n);
     if (workspace_bytes < need) return fail(CVX_ERR_WORKSPACE, "cvx_affine_lts_f32: workspace %zu < %zu bytes", workspace_bytes, need);
     Carver cv(workspace);
@@ -175,23 +175,18 @@ extern "C" int cvx_affine_field_f64(const float* theta, int H, int W, int D, con
     CVX_REQUIRE(H > 0 && W > 0 && D > 0, "cvx_affine_field_f64: bad extent (%dx%dx%d)", H, W, D);
     const size_t V = voxels(H, W, D);
     CVX_REQUIRE(V, "cvx_affine_field_f64: more than 2^31 - 1 voxels (%dx%dx%d)", H, W, D);
-    CVX_REQUIRE(!u || field_strides_ok(u_comp_stride, u_voxel_stride, V), "cvx_affine_field_f64: bad field strides of u (component %lld, voxel %lld)",
-                (long long)u_comp_stride, (long long)u_voxel_stride);
-    CVX_REQUIRE(field_strides_ok(out_comp_stride, out_voxel_stride, V), "cvx_affine_field_f64: bad field strides of out (component %lld, voxel %lld)",
-                (long long)out_comp_stride, (long long)out_voxel_stride);
-    CVX_REQUIRE(field_aligned(theta, 0) && field_aligned(u, u_f64) && field_aligned(out, out_f64),
-                "cvx_affine_field_f64: a buffer is not aligned to its element");
-    const size_t ob = field_bytes(out_comp_stride, out_voxel_stride, V, out_f64);
-    CVX_REQUIRE(!ranges_overlap(out, ob, theta, 48) && (!u || !ranges_overlap(out, ob, u, field_bytes(u_comp_stride, u_voxel_stride, V, u_f64))),
-                "cvx_affine_field_f64: out overlaps an input");
+    const FieldArg fu = {u, u_f64, u_comp_stride, u_voxel_stride}, fo = {out, out_f64, out_comp_stride, out_voxel_stride};
+    CVX_REQUIRE(!u || fu.strides_ok(V), "cvx_affine_field_f64: bad field strides of u (component %lld, voxel %lld)", (long long)u_comp_stride,
+                (long long)u_voxel_stride);
+    CVX_REQUIRE(fo.strides_ok(V), "cvx_affine_field_f64: bad field strides of out (component %lld, voxel %lld)", (long long)out_comp_stride,
+                (long long)out_voxel_stride);
+    CVX_REQUIRE(field_aligned(theta, 0) && fu.aligned() && fo.aligned(), "cvx_affine_field_f64: a buffer is not aligned to its element");
+    const Span ins[2] = {{theta, 48}, fu.span(V)}, outs[1] = {fo.span(V)};
+    CVX_REQUIRE(find_overlaps(outs, ins).out < 0, "cvx_affine_field_f64: out overlaps an input");
     hipStream_t s = as_stream(stream);
     const size_t ucs = u ? (size_t)u_comp_stride : 0, uvs = u ? (size_t)u_voxel_stride : 0, ocs = (size_t)out_comp_stride, ovs = (size_t)out_voxel_stride;
-    if (u && u_f64) {
-        if (out_f64) launch_affine_field<double, double>(theta, H, W, D, u, ucs, uvs, out, ocs, ovs, s);
-        else launch_affine_field<double, float>(theta, H, W, D, u, ucs, uvs, out, ocs, ovs, s);
-    } else {
-        if (out_f64) launch_affine_field<float, double>(theta, H, W, D, u, ucs, uvs, out, ocs, ovs, s);
-        else launch_affine_field<float, float>(theta, H, W, D, u, ucs, uvs, out, ocs, ovs, s);
-    }
+    with_real(u && u_f64, [&](auto tu) {                                        // no u: the float instance, whatever u_f64 says
+        with_real(out_f64, [&](auto to) { launch_affine_field<decltype(tu), decltype(to)>(theta, H, W, D, u, ucs, uvs, out, ocs, ovs, s); });
+    });
     return check_last("affine_field");
 }

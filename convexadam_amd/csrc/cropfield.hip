@@ -220,15 +220,13 @@ extern "C" int cvx_crop_field_half_f32(const float* field, int64_t comp_stride, 
                 S1, S2);
     const size_t Vf = voxels(H, W, D), Vs = voxels(S0, S1, S2);
     CVX_REQUIRE(Vf && Vs, "cvx_crop_field_half_f32: more than 2^31 - 1 voxels (field %dx%dx%d, original %dx%dx%d)", H, W, D, S0, S1, S2);
-    // interleaved [..][3] (strides 1, 3), planar [3][..] (V, 1), or any other layout in which the three components do not fold onto each other
-    const bool stride_range = comp_stride > 0 && voxel_stride > 0 && comp_stride < ((int64_t)1 << 40) && voxel_stride < ((int64_t)1 << 20);
-    CVX_REQUIRE(stride_range && (voxel_stride >= 3 * comp_stride || comp_stride >= (int64_t)Vf * voxel_stride),
-                "cvx_crop_field_half_f32: bad field strides (component %lld, voxel %lld)", (long long)comp_stride, (long long)voxel_stride);
+    const FieldArg f = {field, 0, comp_stride, voxel_stride};
+    CVX_REQUIRE(f.strides_ok(Vf), "cvx_crop_field_half_f32: bad field strides (component %lld, voxel %lld)", (long long)comp_stride,
+                (long long)voxel_stride);
     const size_t esize = out_f32 ? 4 : 2;
-    CVX_REQUIRE(((uintptr_t)out & (esize - 1)) == 0 && ((uintptr_t)field & 3) == 0, "cvx_crop_field_half_f32: a buffer is not aligned to its element");
+    CVX_REQUIRE(((uintptr_t)out & (esize - 1)) == 0 && f.aligned(), "cvx_crop_field_half_f32: a buffer is not aligned to its element");
     const size_t Vo = (size_t)(S0 / 2) * (S1 / 2) * (S2 / 2);
-    const size_t fbytes = (size_t)(2 * comp_stride + (int64_t)(Vf - 1) * voxel_stride + 1) * 4;
-    CVX_REQUIRE(!ranges_overlap(out, 3 * Vo * esize, field, fbytes), "cvx_crop_field_half_f32: out overlaps the field");
+    CVX_REQUIRE(!ranges_overlap(out, 3 * Vo * esize, field, f.bytes(Vf)), "cvx_crop_field_half_f32: out overlaps the field");
     CropGeom G = {};
     if (identity) {
         CVX_REQUIRE(H == S0 && W == S1 && D == S2, "cvx_crop_field_half_f32: shape mismatch (identity mode: field %dx%dx%d, original %dx%dx%d)", H, W,

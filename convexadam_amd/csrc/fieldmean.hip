@@ -146,6 +146,7 @@ static void launch_field_mean(const FieldMeanArgs& a, hipStream_t s) {
                        a.vs, a.V, a.W, a.D, a.quantize, a.mask, static_cast<const TS*>(a.seg), a.sz, a.sy, a.sx, a.g, a.kind, a.ws.sums,
                        a.ws.counts, a.nblocks);
 }
+// the field's element comes from with_real; this holds the mode and the segmentation's element
 template <typename TF>
 static void launch_field_mean_for(const FieldMeanArgs& a, hipStream_t s) {
     if (a.seg) {
@@ -193,23 +194,15 @@ extern "C" int cvx_field_mean_f64(const void* field, int field_is_f64, long long
         CVX_REQUIRE(Vs, "cvx_field_mean_f64: more than 2^31 - 1 voxels (segmentation %dx%dx%d)", sH, sW, sD);
     }
     CVX_REQUIRE(!map12 || all_finite(map12, 12), "cvx_field_mean_f64: non-finite index map");
-    // interleaved [..][3] (strides 1, 3), planar [3][..] (V, 1), or any other layout in which the three components do not fold onto each other
-    const bool stride_range = comp_stride > 0 && voxel_stride > 0 && comp_stride < (1LL << 40) && voxel_stride < (1LL << 20);
-    CVX_REQUIRE(stride_range && (voxel_stride >= 3 * comp_stride || comp_stride >= (long long)V * voxel_stride),
-                "cvx_field_mean_f64: bad field strides (component %lld, voxel %lld)", comp_stride, voxel_stride);
+    const FieldArg f = {field, field_is_f64, comp_stride, voxel_stride};
+    CVX_REQUIRE(f.strides_ok(V), "cvx_field_mean_f64: bad field strides (component %lld, voxel %lld)", comp_stride, voxel_stride);
     const size_t nblocks = (size_t)cdiv64((int64_t)V, FM_SPAN);
     const size_t need = cvx_field_mean_workspace_bytes(H, W, D);
-    const size_t fbytes = (size_t)(2 * comp_stride + (long long)(V - 1) * voxel_stride + 1) * (field_is_f64 ? 8 : 4);
-    const size_t sbytes = Vs * (seg_kind == 1 ? 4 : 8);
-    const struct { const void* p; size_t bytes; } in[3] = {{field, fbytes}, {mask, V}, {seg, sbytes}},
-                                                  out[3] = {{sums3, 3 * sizeof(double)}, {count, sizeof(long long)}, {workspace, need}};
-    for (int o = 0; o < 3; ++o) {
-        if (!out[o].p) continue;
-        for (int i = 0; i < 3; ++i)
-            CVX_REQUIRE(!in[i].p || !ranges_overlap(out[o].p, out[o].bytes, in[i].p, in[i].bytes), "cvx_field_mean_f64: an output overlaps an input");
-        for (int q = o + 1; q < 3; ++q)
-            CVX_REQUIRE(!out[q].p || !ranges_overlap(out[o].p, out[o].bytes, out[q].p, out[q].bytes), "cvx_field_mean_f64: outputs overlap each other");
-    }
+    const Span ins[3] = {f.span(V), {mask, V}, {seg, Vs * (seg_kind == 1 ? 4 : 8)}};
+    const Span outs[3] = {{sums3, 3 * sizeof(double)}, {count, sizeof(long long)}, {workspace, need}};
+    const Overlaps ov = find_overlaps(outs, ins);
+    CVX_REQUIRE(ov.out < 0, "cvx_field_mean_f64: an output overlaps an input");
+    CVX_REQUIRE(ov.a < 0, "cvx_field_mean_f64: outputs overlap each other");
     if (!workspace || workspace_bytes < need)
         return fail(CVX_ERR_WORKSPACE, "cvx_field_mean_f64: workspace %zu < %zu bytes", workspace ? workspace_bytes : (size_t)0, need);
     FieldMeanArgs a;
@@ -222,8 +215,7 @@ extern "C" int cvx_field_mean_f64(const void* field, int field_is_f64, long long
     a.ws = field_mean_layout(cv, nblocks);
     a.nblocks = nblocks;
     hipStream_t s = as_stream(stream);
-    if (field_is_f64) launch_field_mean_for<double>(a, s);
-    else launch_field_mean_for<float>(a, s);
+    with_real(field_is_f64, [&](auto tf) { launch_field_mean_for<decltype(tf)>(a, s); });
     const int st = check_last("cvx_field_mean_f64");
     if (st != CVX_OK) return st;
     hipLaunchKernelGGL(k_field_mean_finish, dim3(1), dim3(FM_THREADS), 0, s, a.ws.sums, a.ws.counts, nblocks, sums3, count);

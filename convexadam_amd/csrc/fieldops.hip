@@ -127,16 +127,6 @@ static void launch_invert(const InvertArgs& a, hipStream_t s) {
     hipLaunchKernelGGL((k_field_invert<TU, TV, B0, B1, B2>), dim3(field_blocks(ft)), dim3(256), 0, s, static_cast<const TU*>(a.u), a.ucs, a.uvs,
                        a.H, a.W, a.D, a.max_iters, a.tol, static_cast<TV*>(a.v), a.vcs, a.vvs, a.residual, a.iters, a.stats, ft);
 }
-template <int B0, int B1, int B2>
-static void launch_invert_for(const InvertArgs& a, bool u64, bool v64, hipStream_t s) {
-    if (u64) {
-        if (v64) launch_invert<double, double, B0, B1, B2>(a, s);
-        else launch_invert<double, float, B0, B1, B2>(a, s);
-    } else {
-        if (v64) launch_invert<float, double, B0, B1, B2>(a, s);
-        else launch_invert<float, float, B0, B1, B2>(a, s);
-    }
-}
 
 struct ComposeArgs { const void *a, *b; size_t acs, avs, bcs, bvs; int H, W, D; void* out; size_t ocs, ovs; };
 
@@ -145,11 +135,6 @@ static void launch_compose(const ComposeArgs& c, hipStream_t s) {
     const FieldTiles ft = field_tiles<FB0, FB1, FB2>(c.H, c.W, c.D);
     hipLaunchKernelGGL((k_field_compose<TA, TB, TO, FB0, FB1, FB2>), dim3(field_blocks(ft)), dim3(256), 0, s, static_cast<const TA*>(c.a), c.acs, c.avs,
                        static_cast<const TB*>(c.b), c.bcs, c.bvs, c.H, c.W, c.D, static_cast<TO*>(c.out), c.ocs, c.ovs, ft);
-}
-template <typename TA, typename TB>
-static void launch_compose_out(const ComposeArgs& c, bool o64, hipStream_t s) {
-    if (o64) launch_compose<TA, TB, double>(c, s);
-    else launch_compose<TA, TB, float>(c, s);
 }
 
 }  // namespace cvx
@@ -163,28 +148,26 @@ extern "C" int cvx_field_invert_f64(const void* u, int u_f64, int64_t u_comp_str
     CVX_REQUIRE(H > 0 && W > 0 && D > 0, "cvx_field_invert_f64: bad extent (%dx%dx%d)", H, W, D);
     const size_t V = voxels(H, W, D);
     CVX_REQUIRE(V, "cvx_field_invert_f64: more than 2^31 - 1 voxels (%dx%dx%d)", H, W, D);
-    CVX_REQUIRE(field_strides_ok(u_comp_stride, u_voxel_stride, V), "cvx_field_invert_f64: bad field strides of u (component %lld, voxel %lld)",
-                (long long)u_comp_stride, (long long)u_voxel_stride);
-    CVX_REQUIRE(field_strides_ok(v_comp_stride, v_voxel_stride, V), "cvx_field_invert_f64: bad field strides of v_out (component %lld, voxel %lld)",
-                (long long)v_comp_stride, (long long)v_voxel_stride);
+    const FieldArg fu = {u, u_f64, u_comp_stride, u_voxel_stride}, fv = {v_out, v_f64, v_comp_stride, v_voxel_stride};
+    CVX_REQUIRE(fu.strides_ok(V), "cvx_field_invert_f64: bad field strides of u (component %lld, voxel %lld)", (long long)u_comp_stride,
+                (long long)u_voxel_stride);
+    CVX_REQUIRE(fv.strides_ok(V), "cvx_field_invert_f64: bad field strides of v_out (component %lld, voxel %lld)", (long long)v_comp_stride,
+                (long long)v_voxel_stride);
     CVX_REQUIRE(max_iters >= 1 && max_iters <= 1000, "cvx_field_invert_f64: max_iters %d outside 1 .. 1000", max_iters);
     CVX_REQUIRE(isfinite(tol) && tol >= 0.0, "cvx_field_invert_f64: tol must be finite and not negative");
-    CVX_REQUIRE(field_aligned(u, u_f64) && field_aligned(v_out, v_f64) && field_aligned(residual, 1) && field_aligned(stats, 1),
+    CVX_REQUIRE(fu.aligned() && fv.aligned() && field_aligned(residual, 1) && field_aligned(stats, 1),
                 "cvx_field_invert_f64: a buffer is not aligned to its element");
-    const size_t ub = field_bytes(u_comp_stride, u_voxel_stride, V, u_f64), vb = field_bytes(v_comp_stride, v_voxel_stride, V, v_f64);
-    const void* outs[4] = {v_out, residual, iters, stats};
-    const size_t bytes[4] = {vb, V * sizeof(double), V, 3 * sizeof(long long)};
-    for (int i = 0; i < 4; ++i) {
-        if (!outs[i]) continue;
-        CVX_REQUIRE(!ranges_overlap(outs[i], bytes[i], u, ub), "cvx_field_invert_f64: an output overlaps u");
-        for (int j = 0; j < i; ++j)
-            CVX_REQUIRE(!outs[j] || !ranges_overlap(outs[i], bytes[i], outs[j], bytes[j]), "cvx_field_invert_f64: two outputs overlap");
-    }
+    const Span ins[1] = {fu.span(V)}, outs[4] = {fv.span(V), {residual, V * sizeof(double)}, {iters, V}, {stats, 3 * sizeof(long long)}};
+    const Overlaps ov = find_overlaps(outs, ins);
+    CVX_REQUIRE(ov.out < 0, "cvx_field_invert_f64: an output overlaps u");
+    CVX_REQUIRE(ov.a < 0, "cvx_field_invert_f64: two outputs overlap");
     hipStream_t s = as_stream(stream);
     if (stats && hipMemsetAsync(stats, 0, 3 * sizeof(long long), s) != hipSuccess) return fail(CVX_ERR_LAUNCH, "cvx_field_invert_f64: memset failed");
     const InvertArgs a = {u, (size_t)u_comp_stride, (size_t)u_voxel_stride, H, W, D, max_iters, tol, v_out, (size_t)v_comp_stride,
                           (size_t)v_voxel_stride, residual, iters, reinterpret_cast<unsigned long long*>(stats)};
-    launch_invert_for<FB0, FB1, FB2>(a, u_f64 != 0, v_f64 != 0, s);
+    with_real(u_f64, [&](auto tu) {
+        with_real(v_f64, [&](auto tv) { launch_invert<decltype(tu), decltype(tv), FB0, FB1, FB2>(a, s); });
+    });
     return check_last("field_invert");
 }
 
@@ -195,27 +178,24 @@ extern "C" int cvx_field_compose_f64(const void* a, int a_f64, int64_t a_comp_st
     CVX_REQUIRE(H > 0 && W > 0 && D > 0, "cvx_field_compose_f64: bad extent (%dx%dx%d)", H, W, D);
     const size_t V = voxels(H, W, D);
     CVX_REQUIRE(V, "cvx_field_compose_f64: more than 2^31 - 1 voxels (%dx%dx%d)", H, W, D);
-    CVX_REQUIRE(field_strides_ok(a_comp_stride, a_voxel_stride, V), "cvx_field_compose_f64: bad field strides of a (component %lld, voxel %lld)",
-                (long long)a_comp_stride, (long long)a_voxel_stride);
-    CVX_REQUIRE(field_strides_ok(b_comp_stride, b_voxel_stride, V), "cvx_field_compose_f64: bad field strides of b (component %lld, voxel %lld)",
-                (long long)b_comp_stride, (long long)b_voxel_stride);
-    CVX_REQUIRE(field_strides_ok(out_comp_stride, out_voxel_stride, V), "cvx_field_compose_f64: bad field strides of out (component %lld, voxel %lld)",
-                (long long)out_comp_stride, (long long)out_voxel_stride);
-    CVX_REQUIRE(field_aligned(a, a_f64) && field_aligned(b, b_f64) && field_aligned(out, out_f64),
-                "cvx_field_compose_f64: a buffer is not aligned to its element");
-    const size_t ob = field_bytes(out_comp_stride, out_voxel_stride, V, out_f64);
-    CVX_REQUIRE(!ranges_overlap(out, ob, a, field_bytes(a_comp_stride, a_voxel_stride, V, a_f64)) &&
-                    !ranges_overlap(out, ob, b, field_bytes(b_comp_stride, b_voxel_stride, V, b_f64)),
+    const FieldArg fa = {a, a_f64, a_comp_stride, a_voxel_stride}, fb = {b, b_f64, b_comp_stride, b_voxel_stride},
+                   fo = {out, out_f64, out_comp_stride, out_voxel_stride};
+    CVX_REQUIRE(fa.strides_ok(V), "cvx_field_compose_f64: bad field strides of a (component %lld, voxel %lld)", (long long)a_comp_stride,
+                (long long)a_voxel_stride);
+    CVX_REQUIRE(fb.strides_ok(V), "cvx_field_compose_f64: bad field strides of b (component %lld, voxel %lld)", (long long)b_comp_stride,
+                (long long)b_voxel_stride);
+    CVX_REQUIRE(fo.strides_ok(V), "cvx_field_compose_f64: bad field strides of out (component %lld, voxel %lld)", (long long)out_comp_stride,
+                (long long)out_voxel_stride);
+    CVX_REQUIRE(fa.aligned() && fb.aligned() && fo.aligned(), "cvx_field_compose_f64: a buffer is not aligned to its element");
+    CVX_REQUIRE(!ranges_overlap(out, fo.bytes(V), a, fa.bytes(V)) && !ranges_overlap(out, fo.bytes(V), b, fb.bytes(V)),
                 "cvx_field_compose_f64: out overlaps an input");
     const ComposeArgs c = {a, b, (size_t)a_comp_stride, (size_t)a_voxel_stride, (size_t)b_comp_stride, (size_t)b_voxel_stride, H, W, D, out,
                            (size_t)out_comp_stride, (size_t)out_voxel_stride};
     hipStream_t s = as_stream(stream);
-    if (a_f64) {
-        if (b_f64) launch_compose_out<double, double>(c, out_f64 != 0, s);
-        else launch_compose_out<double, float>(c, out_f64 != 0, s);
-    } else {
-        if (b_f64) launch_compose_out<float, double>(c, out_f64 != 0, s);
-        else launch_compose_out<float, float>(c, out_f64 != 0, s);
-    }
+    with_real(a_f64, [&](auto ta) {
+        with_real(b_f64, [&](auto tb) {
+            with_real(out_f64, [&](auto to) { launch_compose<decltype(ta), decltype(tb), decltype(to)>(c, s); });
+        });
+    });
     return check_last("field_compose");
 }

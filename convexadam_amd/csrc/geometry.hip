@@ -78,18 +78,6 @@ static void launch_field(const void* field, size_t cs, size_t vs, int fz, int fy
     hipLaunchKernelGGL((k_field_to_grid<TF, TM, TW>), dim3((unsigned)cdiv64((int64_t)V, 256)), dim3(256), 0, s, static_cast<const TF*>(field),
                        cs, vs, fz, fy, fx, g, fr, static_cast<const TM*>(moving), mz, my, mx, carried, static_cast<TW*>(warped));
 }
-template <typename TF>
-static void launch_field_for(const void* field, size_t cs, size_t vs, int fz, int fy, int fx, const IndexMap& g, const FieldFrame& fr,
-                             const void* moving, int moving_f64, int mz, int my, int mx, size_t V, double* carried, void* warped, int warped_f64,
-                             hipStream_t s) {
-    if (moving_f64) {
-        if (warped_f64) launch_field<TF, double, double>(field, cs, vs, fz, fy, fx, g, fr, moving, mz, my, mx, V, carried, warped, s);
-        else launch_field<TF, double, float>(field, cs, vs, fz, fy, fx, g, fr, moving, mz, my, mx, V, carried, warped, s);
-    } else {
-        if (warped_f64) launch_field<TF, float, double>(field, cs, vs, fz, fy, fx, g, fr, moving, mz, my, mx, V, carried, warped, s);
-        else launch_field<TF, float, float>(field, cs, vs, fz, fy, fx, g, fr, moving, mz, my, mx, V, carried, warped, s);
-    }
-}
 
 }  // namespace cvx
 
@@ -106,13 +94,11 @@ extern "C" int cvx_resample_linear_f64(const void* src, int src_f64, int sz, int
     CVX_REQUIRE(all_finite(map12_host, 12) && isfinite(default_value), "cvx_resample_linear_f64: non-finite index map or default value");
     const IndexMap g = make_map(map12_host);
     hipStream_t s = as_stream(stream);
-    if (src_f64) {
-        if (out_f64) launch_resample<double, double>(src, sz, sy, sx, out, oz, oy, ox, Vo, g, default_value, s);
-        else launch_resample<double, float>(src, sz, sy, sx, out, oz, oy, ox, Vo, g, default_value, s);
-    } else {
-        if (out_f64) launch_resample<float, double>(src, sz, sy, sx, out, oz, oy, ox, Vo, g, default_value, s);
-        else launch_resample<float, float>(src, sz, sy, sx, out, oz, oy, ox, Vo, g, default_value, s);
-    }
+    with_real(src_f64, [&](auto ts) {
+        with_real(out_f64, [&](auto to) {
+            launch_resample<decltype(ts), decltype(to)>(src, sz, sy, sx, out, oz, oy, ox, Vo, g, default_value, s);
+        });
+    });
     return check_last("resample_linear");
 }
 
@@ -126,17 +112,15 @@ extern "C" int cvx_field_to_grid_f64(const void* field, int field_f64, int64_t c
     CVX_REQUIRE(fz > 0 && fy > 0 && fx > 0 && mz > 0 && my > 0 && mx > 0, "cvx_field_to_grid_f64: bad extent (field %dx%dx%d, moving %dx%dx%d)", fz, fy,
                 fx, mz, my, mx);
     CVX_REQUIRE(Vf && Vm, "cvx_field_to_grid_f64: more than 2^31 - 1 voxels (field %dx%dx%d, moving %dx%dx%d)", fz, fy, fx, mz, my, mx);
-    // interleaved [..][3] (strides 1, 3), planar [3][..] (V, 1), or any other layout in which the three components do not fold onto each other
-    const bool stride_range = comp_stride > 0 && voxel_stride > 0 && comp_stride < ((int64_t)1 << 40) && voxel_stride < ((int64_t)1 << 20);
-    CVX_REQUIRE(stride_range && (voxel_stride >= 3 * comp_stride || comp_stride >= (int64_t)Vf * voxel_stride),
-                "cvx_field_to_grid_f64: bad field strides (component %lld, voxel %lld)", (long long)comp_stride, (long long)voxel_stride);
-    const size_t fbytes = (size_t)(2 * comp_stride + (int64_t)(Vf - 1) * voxel_stride + 1) * (field_f64 ? 8 : 4);
-    const size_t mbytes = Vm * (moving_f64 ? 8 : 4), cbytes = Vm * 3 * sizeof(double), wbytes = Vm * (warped_f64 ? 8 : 4);
-    CVX_REQUIRE(!carried || (!ranges_overlap(carried, cbytes, field, fbytes) && !(moving && ranges_overlap(carried, cbytes, moving, mbytes))),
-                "cvx_field_to_grid_f64: carried overlaps an input");
-    CVX_REQUIRE(!warped || (!ranges_overlap(warped, wbytes, field, fbytes) && !ranges_overlap(warped, wbytes, moving, mbytes)),
-                "cvx_field_to_grid_f64: warped overlaps an input");
-    CVX_REQUIRE(!(carried && warped) || !ranges_overlap(carried, cbytes, warped, wbytes), "cvx_field_to_grid_f64: the two outputs overlap");
+    const FieldArg f = {field, field_f64, comp_stride, voxel_stride};
+    CVX_REQUIRE(f.strides_ok(Vf), "cvx_field_to_grid_f64: bad field strides (component %lld, voxel %lld)", (long long)comp_stride,
+                (long long)voxel_stride);
+    const Span ins[2] = {f.span(Vf), {moving, Vm * (moving_f64 ? 8 : 4)}};
+    const Span outs[2] = {{carried, Vm * 3 * sizeof(double)}, {warped, Vm * (warped_f64 ? 8 : 4)}};
+    const Overlaps ov = find_overlaps(outs, ins);
+    CVX_REQUIRE(ov.out != 0, "cvx_field_to_grid_f64: carried overlaps an input");
+    CVX_REQUIRE(ov.out != 1, "cvx_field_to_grid_f64: warped overlaps an input");
+    CVX_REQUIRE(ov.a < 0, "cvx_field_to_grid_f64: the two outputs overlap");
     CVX_REQUIRE(all_finite(map12_host, 12) && all_finite(rot9_host, 9) && all_finite(ratio3_host, 3),
                 "cvx_field_to_grid_f64: non-finite index map, rotation or spacing ratio");
     const IndexMap g = make_map(map12_host);
@@ -145,7 +129,12 @@ extern "C" int cvx_field_to_grid_f64(const void* field, int field_f64, int64_t c
     for (int i = 0; i < 3; ++i) fr.ratio[i] = ratio3_host[i];
     hipStream_t s = as_stream(stream);
     const size_t cs = (size_t)comp_stride, vs = (size_t)voxel_stride;
-    if (field_f64) launch_field_for<double>(field, cs, vs, fz, fy, fx, g, fr, moving, moving_f64, mz, my, mx, Vm, carried, warped, warped_f64, s);
-    else launch_field_for<float>(field, cs, vs, fz, fy, fx, g, fr, moving, moving_f64, mz, my, mx, Vm, carried, warped, warped_f64, s);
+    with_real(field_f64, [&](auto tf) {
+        with_real(moving_f64, [&](auto tm) {
+            with_real(warped_f64, [&](auto tw) {
+                launch_field<decltype(tf), decltype(tm), decltype(tw)>(field, cs, vs, fz, fy, fx, g, fr, moving, mz, my, mx, Vm, carried, warped, s);
+            });
+        });
+    });
     return check_last("field_to_grid");
 }

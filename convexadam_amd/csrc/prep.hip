@@ -504,8 +504,6 @@ static MaskWs mask_layout(Carver& c, size_t V) {
     return w;
 }
 
-static bool overlap_any(const void* a, size_t ab, const void* b, size_t bb) { return a && b && ranges_overlap(a, ab, b, bb); }
-
 }  // namespace cvx
 
 using namespace cvx;
@@ -552,12 +550,10 @@ extern "C" int cvx_prep_stats_f32(const float* x, long long n, int flags, float 
                     "cvx_prep_stats_f32: quantile fractions outside [0, 1] (%g, %g)", (double)q0, (double)q1);
     }
     const size_t need = cvx_prep_stats_workspace_bytes(n), xbytes = (size_t)n * 4;
-    const struct { const void* p; size_t bytes; } out[3] = {{params, 16}, {moments3, 24}, {workspace, need}};
-    for (int o = 0; o < 3; ++o) {
-        CVX_REQUIRE(!overlap_any(out[o].p, out[o].bytes, x, xbytes), "cvx_prep_stats_f32: an output overlaps x");
-        for (int q = o + 1; q < 3; ++q)
-            CVX_REQUIRE(!overlap_any(out[o].p, out[o].bytes, out[q].p, out[q].bytes), "cvx_prep_stats_f32: outputs overlap each other");
-    }
+    const Span ins[1] = {{x, xbytes}}, outs[3] = {{params, 16}, {moments3, 24}, {workspace, need}};
+    const Overlaps ov = find_overlaps(outs, ins);
+    CVX_REQUIRE(ov.out < 0, "cvx_prep_stats_f32: an output overlaps x");
+    CVX_REQUIRE(ov.a < 0, "cvx_prep_stats_f32: outputs overlap each other");
     if (!workspace || workspace_bytes < need)
         return fail(CVX_ERR_WORKSPACE, "cvx_prep_stats_f32: workspace %zu < %zu bytes", workspace ? workspace_bytes : (size_t)0, need);
     const size_t nspans = (size_t)cdiv64(n, PR_SPAN);
@@ -634,12 +630,10 @@ extern "C" int cvx_prep_nonzero_mask_u8(const float* data, int C, int H, int W, 
     CVX_REQUIRE((uint64_t)V * (uint64_t)C < ((uint64_t)1 << 40), "cvx_prep_nonzero_mask_u8: %d channels of %dx%dx%d are 2^40 elements or more", C, H, W, D);
     CVX_REQUIRE(ndim == 3 || (ndim == 2 && H == 1), "cvx_prep_nonzero_mask_u8: ndim %d (3, or 2 with H = 1)", ndim);
     const size_t need = cvx_prep_nonzero_mask_workspace_bytes(H, W, D), dbytes = (size_t)C * V * 4;
-    const struct { const void* p; size_t bytes; } out[4] = {{mask_out, V}, {box6, 24}, {count, 8}, {workspace, need}};
-    for (int o = 0; o < 4; ++o) {
-        CVX_REQUIRE(!overlap_any(out[o].p, out[o].bytes, data, dbytes), "cvx_prep_nonzero_mask_u8: an output overlaps data");
-        for (int q = o + 1; q < 4; ++q)
-            CVX_REQUIRE(!overlap_any(out[o].p, out[o].bytes, out[q].p, out[q].bytes), "cvx_prep_nonzero_mask_u8: outputs overlap each other");
-    }
+    const Span ins[1] = {{data, dbytes}}, outs[4] = {{mask_out, V}, {box6, 24}, {count, 8}, {workspace, need}};
+    const Overlaps ov = find_overlaps(outs, ins);
+    CVX_REQUIRE(ov.out < 0, "cvx_prep_nonzero_mask_u8: an output overlaps data");
+    CVX_REQUIRE(ov.a < 0, "cvx_prep_nonzero_mask_u8: outputs overlap each other");
     if (!workspace || workspace_bytes < need)
         return fail(CVX_ERR_WORKSPACE, "cvx_prep_nonzero_mask_u8: workspace %zu < %zu bytes", workspace ? workspace_bytes : (size_t)0, need);
     Carver cv(workspace);

@@ -145,11 +145,10 @@ extern "C" int cvx_ranksum_better_f64(const double* samples, const float* means,
     CVX_REQUIRE(((uintptr_t)samples & 7) == 0 && ((uintptr_t)means & 3) == 0 && ((uintptr_t)scores & 3) == 0 && ((uintptr_t)u2 & 3) == 0,
                 "cvx_ranksum_better_f64: a buffer is not aligned to its element");
     const size_t sbytes = (size_t)n_samples * 8, obytes = (size_t)R * N * 4, ubytes = (size_t)n_u2 * 4, mbytes = (size_t)N * 4;
-    CVX_REQUIRE(!ranges_overlap(scores, obytes, samples, sbytes) && !(u2 && ranges_overlap(u2, ubytes, samples, sbytes)) &&
-                    !(u2 && ranges_overlap(u2, ubytes, scores, obytes)),
-                "cvx_ranksum_better_f64: scores, u2 and samples overlap");
-    CVX_REQUIRE(!means || (!ranges_overlap(scores, obytes, means, mbytes) && !(u2 && ranges_overlap(u2, ubytes, means, mbytes))),
-                "cvx_ranksum_better_f64: an output overlaps means");
+    const Span outs[2] = {{scores, obytes}, {u2, ubytes}}, in_samples[1] = {{samples, sbytes}}, in_means[1] = {{means, mbytes}};
+    const Overlaps ov = find_overlaps(outs, in_samples);
+    CVX_REQUIRE(ov.out < 0 && ov.a < 0, "cvx_ranksum_better_f64: scores, u2 and samples overlap");
+    CVX_REQUIRE(find_overlaps(outs, in_means).out < 0, "cvx_ranksum_better_f64: an output overlaps means");
     hipStream_t s = as_stream(stream);
     if (S <= 64) launch_ranksum<1>(samples, means, scale, sign, R, N, S, u2_crit, scores, u2, s);
     else if (S <= 128) launch_ranksum<2>(samples, means, scale, sign, R, N, S, u2_crit, scores, u2, s);

@@ -19,6 +19,7 @@
 // Means: every thread adds its column's values in float64 in plane order, a workgroup adds its SSIM_TW rows per D column in row order and
 // writes SSIM_TD float64 partials; k_ssim_finish adds the partials in index order.  No atomics: the same bits on every run.
 #include "cvx_common.h"
+#include "geometry_args.h"
 
 namespace cvx {
 
@@ -277,11 +278,6 @@ static SsimTaps ssim_taps(int ws) {
     return taps;
 }
 
-static bool ranges_overlap(const void* a, const void* b, size_t bytes) {
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return pa < pb + bytes && pb < pa + bytes;
-}
-
 // every refusal of the two entry points (0 = acceptable); `what` names the caller in the message
 static int ssim_check(const char* what, int n, int c, int h, int w, int d, int ws) {
     CVX_REQUIRE(n > 0 && c > 0 && h > 0 && w > 0 && d > 0, "%s: bad extent (%d, %d, %d, %d, %d)", what, n, c, h, w, d);
@@ -311,7 +307,7 @@ extern "C" int cvx_ssim3d_f32(const float* img1, const float* img2, int n, int c
     if (rc != CVX_OK) return rc;
     const int64_t nc = (int64_t)n * c;
     const size_t bytes = (size_t)nc * h * w * d * sizeof(float);
-    CVX_REQUIRE(!map || (!ranges_overlap(map, img1, bytes) && !ranges_overlap(map, img2, bytes)), "cvx_ssim3d_f32: map overlaps an input (every voxel is read by its neighbours' windows)");
+    CVX_REQUIRE(!overlap_any(map, bytes, img1, bytes) && !overlap_any(map, bytes, img2, bytes), "cvx_ssim3d_f32: map overlaps an input (every voxel is read by its neighbours' windows)");
     const SsimPlan p = ssim_plan(nc, h, w, d);
     double* partial = nullptr;
     if (mean || slice_mean) {                                               // the map alone needs no workspace

@@ -20,38 +20,7 @@ import numpy as np
 import torch
 
 from . import _field
-from ._lib import check, ptr, stream_ptr
-from .convex_adam_utils import validate_image
-
-
-def _device_field(t, name):
-    """a device tensor as the kernels read it -> (contiguous float32 / float64 tensor, (H, W, D), component stride, voxel stride)"""
-    t = t.detach()
-    if t.dim() != 4 or (t.shape[-1] != 3 and t.shape[0] != 3):
-        raise ValueError("%s must be (H, W, D, 3) or (3, H, W, D), got %s" % (name, tuple(t.shape)))
-    if t.dtype not in (torch.float32, torch.float64):
-        t = t.to(torch.float64)
-    t = t.contiguous()
-    if t.shape[-1] == 3:                                   # (3, 3, 3, 3) reads as (H, W, D, 3), what convex_adam_pt returns
-        shape = tuple(int(n) for n in t.shape[:3])
-        return t, shape, 1, 3
-    shape = tuple(int(n) for n in t.shape[1:])
-    return t, shape, shape[0] * shape[1] * shape[2], 1
-
-
-def _operand(f, name, device):
-    """-> (device tensor, shape, cs, vs, came from the host)"""
-    if isinstance(f, torch.Tensor) and f.is_cuda:
-        return _device_field(f, name) + (False,)
-    t = validate_image(f)
-    if t.dim() != 4 or t.shape[-1] != 3:
-        raise ValueError("%s must be (H, W, D, 3), got %s" % (name, tuple(t.shape)))
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-    return _device_field(t.to(dev, torch.float64), name) + (True,)
-
-
-def _f64(t):
-    return int(t.dtype == torch.float64)
+from ._lib import check, field_operand_from, ptr, stream_ptr
 
 
 def invert_field(disp, max_iters=50, tol=1e-4, return_info=False, device=None):
@@ -64,7 +33,7 @@ def invert_field(disp, max_iters=50, tol=1e-4, return_info=False, device=None):
     return_info=True also returns dict(residual, iters, not_converged, non_finite, max_residual): per voxel the max-norm of
     compose_fields(disp, v) and the iterations it ran (arrays like the result: numpy or device tensors), the number of voxels that never
     met `tol`, the number whose coordinates were not finite (they hold NaN), and the largest finite residual."""
-    u, shape, cs, vs, host = _operand(disp, "disp", device)
+    u, shape, cs, vs, f64, host = field_operand_from(disp, "disp", device)
     dev = u.device
     out_dtype = disp.dtype if not host else torch.float64
     v = torch.empty_like(u)
@@ -72,8 +41,8 @@ def invert_field(disp, max_iters=50, tol=1e-4, return_info=False, device=None):
     iters = torch.empty(shape, dtype=torch.uint8, device=dev) if return_info else None
     stats = torch.empty(3, dtype=torch.int64, device=dev) if return_info else None
     with torch.cuda.device(dev):
-        check(_field.lib().cvx_field_invert_f64(ptr(u), _f64(u), cs, vs, shape[0], shape[1], shape[2], int(max_iters), float(tol), ptr(v),
-                                                _f64(v), cs, vs, ptr(residual), ptr(iters), ptr(stats), stream_ptr(dev)))
+        check(_field.lib().cvx_field_invert_f64(ptr(u), f64, cs, vs, shape[0], shape[1], shape[2], int(max_iters), float(tol), ptr(v), f64,
+                                                cs, vs, ptr(residual), ptr(iters), ptr(stats), stream_ptr(dev)))
     v = v.cpu().numpy() if host else v.to(out_dtype)
     if not return_info:
         return v
@@ -88,14 +57,14 @@ def compose_fields(first, second, device=None):
     out(x) = second(x) + first(x + second(x)), so that apply_convex(second, apply_convex(first, img)) ~ apply_convex(out, img).
     Both fields live on the same grid.  Host inputs give a float64 numpy array; if `first` is a device tensor the result is a device
     tensor of its layout and dtype (`second` may use the other layout or element type)."""
-    a, shape, acs, avs, host = _operand(first, "first", device)
-    b, bshape, bcs, bvs, _ = _operand(second, "second", a.device)
+    a, shape, acs, avs, a64, host = field_operand_from(first, "first", device)
+    b, bshape, bcs, bvs, b64, _ = field_operand_from(second, "second", a.device)
     if bshape != shape or b.device != a.device:
         raise ValueError("compose_fields: first is %s on %s, second %s on %s" % (shape, a.device, bshape, b.device))
     out = torch.empty_like(a)
     with torch.cuda.device(a.device):
-        check(_field.lib().cvx_field_compose_f64(ptr(a), _f64(a), acs, avs, ptr(b), _f64(b), bcs, bvs, shape[0], shape[1], shape[2], ptr(out),
-                                                 _f64(out), acs, avs, stream_ptr(a.device)))
+        check(_field.lib().cvx_field_compose_f64(ptr(a), a64, acs, avs, ptr(b), b64, bcs, bvs, shape[0], shape[1], shape[2], ptr(out), a64,
+                                                 acs, avs, stream_ptr(a.device)))
     return out.cpu().numpy() if host else out.to(first.dtype)
 
 

@@ -20,7 +20,7 @@ from collections import namedtuple
 import numpy as np
 import torch
 
-from ._lib import check, lib, ptr, require_device_tensor, stream_ptr, workspace
+from ._lib import check, field_operand, lib, ptr, require_device_tensor, stream_ptr, workspace
 
 Grid = namedtuple("Grid", "size spacing origin direction")          # x, y, z; direction: 9 values, row-major
 Registration = namedtuple("Registration", "field carried_field warped ssim_before ssim_after")
@@ -84,15 +84,6 @@ def resample_device(src, src_grid, out_grid, default=0.0):
     return torch.round(out).to(src.dtype)                       # torch.round: half to even
 
 
-def _field_layout(f, shape):
-    """(component stride, voxel stride) in elements of a contiguous (H, W, D, 3) or (3, H, W, D) field on a grid of (z, y, x) = shape"""
-    if f.dim() == 4 and tuple(f.shape) == tuple(shape) + (3,):
-        return 1, 3
-    if f.dim() == 4 and tuple(f.shape) == (3,) + tuple(shape):
-        return shape[0] * shape[1] * shape[2], 1
-    raise ValueError("field must be (H, W, D, 3) or (3, H, W, D) on the grid (z, y, x) = %s, got %s" % (tuple(shape), tuple(f.shape)))
-
-
 def field_frame(moving_grid, fixed_grid, fixed_resampled_grid):
     """R = inv(D_fixed) @ D_moving and ratio = spacing(resampled fixed) / spacing(moving), x, y, z order (convex_adam_utils.py:340-351)."""
     frame_fixed = np.array(grid_of(fixed_grid).direction).reshape(3, 3)
@@ -113,12 +104,7 @@ def rescale_displacement_field_device(field, moving_grid, fixed_grid, fixed_resa
     and returns the warped volume alone."""
     require_device_tensor(field, "field")
     mg, fg, rg = grid_of(moving_grid), grid_of(fixed_grid), grid_of(fixed_resampled_grid)
-    shape = tuple(rg.size)[::-1]
-    f = field.detach()
-    if f.dtype not in (torch.float32, torch.float64):
-        f = f.to(torch.float64)
-    f = f.contiguous()
-    cs, vs = _field_layout(f, shape)
+    f, shape, cs, vs, f64 = field_operand(field, tuple(rg.size)[::-1])
     dev = f.device
     mx, my, mz = mg.size
     m, m64 = (None, 0)
@@ -136,7 +122,7 @@ def rescale_displacement_field_device(field, moving_grid, fixed_grid, fixed_resa
     M, t = index_map(rg, mg)
     rot, ratio = field_frame(mg, fg, rg)
     with torch.cuda.device(dev):
-        check(lib().cvx_field_to_grid_f64(ptr(f), int(f.dtype == torch.float64), cs, vs, shape[0], shape[1], shape[2], _doubles(M, t),
+        check(lib().cvx_field_to_grid_f64(ptr(f), f64, cs, vs, shape[0], shape[1], shape[2], _doubles(M, t),
                                           _doubles(rot), _doubles(ratio), ptr(m), m64, mz, my, mx, ptr(carried), ptr(warped),
                                           int(warped_dtype == torch.float64), stream_ptr(dev)))
     if moving is None:
@@ -168,25 +154,10 @@ def field_mean_buffer(field, field_grid=None, mask=None, seg=None, seg_grid=None
     """field_mean_device's result as the one device buffer the kernel wrote: float64[4], the three sums and the bits of the int64 count
     (for a caller that downloads all 32 bytes at once)."""
     require_device_tensor(field, "field")
-    f = field.detach()
-    if f.dim() != 4:
-        raise ValueError("field must be (H, W, D, 3) or (3, H, W, D), got %s" % (tuple(f.shape),))
-    if field_grid is not None:
-        shape = tuple(grid_of(field_grid).size)[::-1]
-    elif mask is not None:
-        shape = tuple(mask.shape)
-    elif f.shape[0] == 3 and f.shape[3] != 3:
-        shape = tuple(f.shape[1:])
-    elif f.shape[3] == 3 and f.shape[0] != 3:
-        shape = tuple(f.shape[:3])
-    else:
-        raise ValueError("a field of shape %s does not say which of its layouts it is: pass field_grid" % (tuple(f.shape),))
     if quantize not in _QUANTIZE:
         raise ValueError("quantize must be None / torch.float32 / 0, or torch.float16 / 1")
-    if f.dtype not in (torch.float32, torch.float64):
-        f = f.to(torch.float64)
-    f = f.contiguous()
-    cs, vs = _field_layout(f, shape)
+    grid = tuple(grid_of(field_grid).size)[::-1] if field_grid is not None else tuple(mask.shape) if mask is not None else None
+    f, shape, cs, vs, f64 = field_operand(field, grid, strict=True)         # no grid, no mask: the shape itself has to say the layout
     dev = f.device
     if mask is not None and seg is not None:
         raise ValueError("mask and seg exclude each other")
@@ -217,7 +188,7 @@ def field_mean_buffer(field, field_grid=None, mask=None, seg=None, seg_grid=None
         if nbytes == 0:
             check(-1)
         buf = workspace(nbytes, dev)
-        check(L.cvx_field_mean_f64(ptr(f), int(f.dtype == torch.float64), cs, vs, shape[0], shape[1], shape[2], _QUANTIZE[quantize], ptr(m), ptr(s),
+        check(L.cvx_field_mean_f64(ptr(f), f64, cs, vs, shape[0], shape[1], shape[2], _QUANTIZE[quantize], ptr(m), ptr(s),
                                    kind, sext[0], sext[1], sext[2], m12, C.c_void_p(out.data_ptr()), C.c_void_p(out.data_ptr() + 24), ptr(buf),
                                    buf.numel(), stream_ptr(dev)))
     return out

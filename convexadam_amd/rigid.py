@@ -8,43 +8,55 @@ import ctypes as C
 
 import torch
 
-from ._lib import CVX_ERR_INVALID_ARG, check, f32c, lib, ptr, require_device_tensor, stream_ptr, workspace
-from .tps import _shape
+from ._lib import CVX_ERR_INVALID_ARG, _shape, check, f32c, lib, ptr, require_device_tensor, stream_ptr, workspace
 
 _MODES = {"bilinear": 0, "nearest": 1}
 
 
-def _points(t, name, exact_cols=None):
-    s = _shape(t, name)
-    if len(s) != 2 or s[0] < 2 or (s[1] != exact_cols if exact_cols else s[1] < 3):
-        want = "(N, %d)" % exact_cols if exact_cols else "(N, k) with k >= 3"
-        raise ValueError("%s must be %s and N >= 2, got %s" % (name, want, s))
-    return s
+def _point_pair(a, b, names, min_n, exact_cols=None):
+    """N of two point sets of one length, from the metadata only: (N, exact_cols), or (N, k >= 3), and N >= min_n"""
+    want = "(N, %d)" % exact_cols if exact_cols else "(N, k) with k >= 3"
+    n = []
+    for t, name in zip((a, b), names):
+        s = _shape(t, name)
+        if len(s) != 2 or s[0] < min_n or (s[1] != exact_cols if exact_cols else s[1] < 3):
+            raise ValueError("%s must be %s and N >= %d, got %s" % (name, want, min_n, s))
+        n.append(s[0])
+    if n[0] != n[1]:
+        raise ValueError("%s and %s must have the same number of points, got %d and %d" % (names + tuple(n)))
+    return n[0]
 
 
-def _fit(fixed, moving, iters, want_inliers):
+def _fit(library, entry, fixed, moving, want_inliers, *model_args):
+    """One launch of library().<entry>_f32 (cvx_rigid_lts, cvx_affine_lts) -> X (4, 4) float32[, the (N,) bool inlier mask]; model_args:
+    what the entry point takes between n and X (iters; the affine one also `normal`)"""
     f = f32c(require_device_tensor(fixed, "fixed"))
     m = f32c(require_device_tensor(moving, "moving"))
     if m.device != f.device:
         raise ValueError("both point sets must live on one device (%s, %s)" % (f.device, m.device))
     n = int(f.shape[0])
-    T = torch.empty((4, 4), dtype=torch.float32, device=f.device)
+    X = torch.empty((4, 4), dtype=torch.float32, device=f.device)
     mask = torch.empty(n, dtype=torch.uint8, device=f.device) if want_inliers else None
+    L = library()
     with torch.cuda.device(f.device):
-        nws = lib().cvx_rigid_lts_workspace_bytes(n)
+        nws = getattr(L, entry + "_workspace_bytes")(n)
         ws = workspace(nws, f.device)
-        check(lib().cvx_rigid_lts_f32(ptr(f), int(f.shape[1]), ptr(m), int(m.shape[1]), n, int(iters), ptr(T), ptr(mask), ptr(ws), nws,
-                                      stream_ptr(f.device)))
-    return (T, mask.bool()) if want_inliers else T
+        check(getattr(L, entry + "_f32")(ptr(f), int(f.shape[1]), ptr(m), int(m.shape[1]), n, *model_args, ptr(X), ptr(mask), ptr(ws), nws,
+                                         stream_ptr(f.device)))
+    return (X, mask.bool()) if want_inliers else X
+
+
+def _trimmed_iters(iter):
+    if int(iter) < 1:
+        raise ValueError("iter must be >= 1, got %r" % (iter,))
+    return int(iter)
 
 
 def find_rigid_3d(x, y):
     """(4, 4) T = [R t; 0 0 0 1] with y[:, :3] ~ x[:, :3] R^T + t, R the optimal proper rotation (convex_adam_utils.py:173-184).
     x, y: (N, k >= 3) device tensors, N >= 2.  Raises CvxError on a non-finite coordinate (the reference's torch.svd raises too)."""
-    sx, sy = _points(x, "x"), _points(y, "y")
-    if sx[0] != sy[0]:
-        raise ValueError("x and y must have the same number of points, got %d and %d" % (sx[0], sy[0]))
-    return _fit(x, y, 1, False)
+    _point_pair(x, y, ("x", "y"), 2)
+    return _fit(lib, "cvx_rigid_lts", x, y, False, 1)
 
 
 def least_trimmed_rigid(fixed_pts, moving_pts, iter=5, return_inliers=False):
@@ -52,12 +64,8 @@ def least_trimmed_rigid(fixed_pts, moving_pts, iter=5, return_inliers=False):
     points with the smallest residuals ||moving - fixed T^T|| under the previous fit (ties: lowest index first).  fixed_pts, moving_pts:
     (N, 4) device tensors (homogeneous points).  Returns T (4, 4) float32, and with return_inliers=True also the (N,) bool mask of the
     points the returned fit used."""
-    sf, sm = _points(fixed_pts, "fixed_pts", 4), _points(moving_pts, "moving_pts", 4)
-    if sf[0] != sm[0]:
-        raise ValueError("fixed_pts and moving_pts must have the same number of points, got %d and %d" % (sf[0], sm[0]))
-    if int(iter) < 1:
-        raise ValueError("iter must be >= 1, got %r" % (iter,))
-    return _fit(fixed_pts, moving_pts, int(iter), bool(return_inliers))
+    _point_pair(fixed_pts, moving_pts, ("fixed_pts", "moving_pts"), 2, 4)
+    return _fit(lib, "cvx_rigid_lts", fixed_pts, moving_pts, bool(return_inliers), _trimmed_iters(iter))
 
 
 def affine_warp(vol, theta, size=None, mode="bilinear"):
@@ -260,7 +268,7 @@ def rigid_samples(coarse_field, mask_coarse, grid_sp, shape):
     return T1[:M], T2[:M]
 
 
-# convex_adam_rigid takes its rigid-fit rows from the coarse field (rigid_samples); False = from the up-sampled field (_field_samples),
+# convex_adam_rigid and convex_adam_affine take the rows of their fit from the coarse field (rigid_samples); False = from the up-sampled field (_field_samples),
 # the same bits -- kept as a switch so that tools/time_rigidreg.py can time both in one process
 SAMPLE_FROM_COARSE = True
 
@@ -291,6 +299,19 @@ def convex_adam_rigid(img_fixed, imgs_moving, mind_r=3, mind_d=3, grid_sp=6, dis
     F.affine_grid(A)) (pull-back convention): F.affine_grid(T[:3]) / affine_warp(moving, T) bring the moving image onto the fixed one.
     The search works on whole coarse cells: a motion below about half a cell (2-3 voxels at grid_sp 6) returns an all-zero coarse
     field and the identity; motions beyond grid_sp * disp_hw voxels are out of reach."""
+    return _register(least_trimmed_rigid, 2, "rigid", RigidRegistration, "tre_rigid", img_fixed, imgs_moving, mind_r, mind_d, grid_sp, disp_hw,
+                     mask_thresh, ic_iters, lts_iters, seg_fixed, seg_moving, return_field)
+
+
+_NO_ROUNDS = object()
+
+
+def _register(fit, min_cells, model, result, tre_name, img_fixed, imgs_moving, mind_r, mind_d, grid_sp, disp_hw, mask_thresh, ic_iters,
+              lts_iters, seg_fixed, seg_moving, return_field, rounds=_NO_ROUNDS):
+    """convex_adam_rigid and convex_adam_affine: features, masks, the convex stage, the rows of the fit, `fit(T1, T2, lts_iters)` on at
+    least `min_cells` coarse cells, and the three landmark errors, the third as `result.<tre_name>`.  `model` is the fit's word in the
+    messages.  rounds: _NO_ROUNDS for a model without that argument (one round, and no message names it); else the stage and the fit run
+    again on the moving images warped with the current T, and the matrices are multiplied in float64 on the device (T <- T T_round)."""
     from .convex_adam_utils import mind_pooled
     movs = list(imgs_moving) if isinstance(imgs_moving, (list, tuple)) else [imgs_moving]
     if not movs:
@@ -299,14 +320,17 @@ def convex_adam_rigid(img_fixed, imgs_moving, mind_r=3, mind_d=3, grid_sp=6, dis
     for i, mv in enumerate(movs):
         if _volume(mv, "imgs_moving[%d]" % i) != shape:
             raise ValueError("imgs_moving[%d] has extent %s, the fixed image %s" % (i, _volume(mv, "imgs_moving[%d]" % i), shape))
+    given = (grid_sp, disp_hw, ic_iters, lts_iters) + (() if rounds is _NO_ROUNDS else (rounds,))
     try:
         g, hw, it, lts = int(grid_sp), int(disp_hw), int(ic_iters), int(lts_iters)
+        nr = 1 if rounds is _NO_ROUNDS else int(rounds)
         thr = float(mask_thresh)
     except (TypeError, ValueError):
-        raise ValueError("grid_sp, disp_hw, ic_iters, lts_iters must be ints and mask_thresh a number") from None
-    if not 1 <= g <= 64 or min(shape) < 2 * g or hw < 0 or it < 0 or lts < 1:
-        raise ValueError("need 1 <= grid_sp <= 64 with at least two cells per axis of %s, disp_hw >= 0, ic_iters >= 0, lts_iters >= 1; got %r, %r, %r, %r"
-                         % (shape, grid_sp, disp_hw, ic_iters, lts_iters))
+        raise ValueError("grid_sp, disp_hw, ic_iters, lts_iters%s must be ints and mask_thresh a number"
+                         % ("" if rounds is _NO_ROUNDS else ", rounds")) from None
+    if not 1 <= g <= 64 or min(shape) < 2 * g or hw < 0 or it < 0 or lts < 1 or nr < 1:
+        raise ValueError("need 1 <= grid_sp <= 64 with at least two cells per axis of %s, disp_hw >= 0, ic_iters >= 0, lts_iters >= 1%s; got %s"
+                         % (shape, "" if rounds is _NO_ROUNDS else ", rounds >= 1", ", ".join(repr(v) for v in given)))
     if (seg_fixed is None) != (seg_moving is None):
         raise ValueError("seg_fixed and seg_moving go together")
     if seg_fixed is not None and (_volume(seg_fixed, "seg_fixed") != shape or _volume(seg_moving, "seg_moving") != shape):
@@ -314,21 +338,30 @@ def convex_adam_rigid(img_fixed, imgs_moving, mind_r=3, mind_d=3, grid_sp=6, dis
     fix = f32c(require_device_tensor(img_fixed, "img_fixed")).reshape(shape)
     movs = [f32c(require_device_tensor(mv, "imgs_moving[%d]" % i)).reshape(shape) for i, mv in enumerate(movs)]
     dev = fix.device
-    ff = mind_pooled(fix[None, None], mind_r, mind_d, g, device=dev)
-    feat_fix = torch.cat([ff] * len(movs), 1) if len(movs) > 1 else ff
-    feat_mov = torch.cat([mind_pooled(mv[None, None], mind_r, mind_d, g, device=dev) for mv in movs], 1)
-    mask_fix, mask_mov = threshold_pool_mask(fix, thr, g), threshold_pool_mask(movs[0], thr, g)
-    kept = int(mask_fix.sum())
-    if kept < 2:
-        raise ValueError("mask_thresh = %r keeps %d coarse cells of the fixed image; the rigid fit needs at least 2" % (mask_thresh, kept))
+
+    def one_round(movs, want_field):
+        """one masked convex stage and one trimmed fit -> (T, mask_fix, mask_mov, disp_hr)"""
+        ff = mind_pooled(fix[None, None], mind_r, mind_d, g, device=dev)
+        feat_fix = torch.cat([ff] * len(movs), 1) if len(movs) > 1 else ff
+        feat_mov = torch.cat([mind_pooled(mv[None, None], mind_r, mind_d, g, device=dev) for mv in movs], 1)
+        mask_fix, mask_mov = threshold_pool_mask(fix, thr, g), threshold_pool_mask(movs[0], thr, g)
+        kept = int(mask_fix.sum())
+        if kept < min_cells:
+            raise ValueError("mask_thresh = %r keeps %d coarse cells of the fixed image; the %s fit needs at least %d"
+                             % (mask_thresh, kept, model, min_cells))
+        coarse, disp_hr = convex_stage(feat_fix, feat_mov, g, hw, shape, mask_fix, mask_mov, it, full_res=want_field or not SAMPLE_FROM_COARSE)
+        if SAMPLE_FROM_COARSE:                  # same rows, bit for bit; a call without the field never forms it at full resolution
+            T1, T2 = rigid_samples(coarse if it > 0 else coarse * g, mask_fix, g, shape)
+        else:
+            T1, T2 = _field_samples(disp_hr, mask_fix, g)
+        return fit(T1, T2, lts), mask_fix, mask_mov, disp_hr
+
     want_field = bool(return_field) or seg_fixed is not None
-    coarse, disp_hr = convex_stage(feat_fix, feat_mov, g, hw, shape, mask_fix, mask_mov, it, full_res=want_field or not SAMPLE_FROM_COARSE)
-    if SAMPLE_FROM_COARSE:                      # same rows, bit for bit; the rigid-only call never forms the full-resolution field
-        T1, T2 = rigid_samples(coarse if it > 0 else coarse * g, mask_fix, g, shape)
-    else:
-        T1, T2 = _field_samples(disp_hr, mask_fix, g)
-    T = least_trimmed_rigid(T1, T2, lts)
-    res = RigidRegistration(T, mask_fix, mask_mov, disp_hr if want_field else None)
+    T, mask_fix, mask_mov, disp_hr = one_round(movs, want_field)
+    for _ in range(1, nr):
+        Tr = one_round([affine_warp(mv[None], T)[0] for mv in movs], False)[0]
+        T = (T.double() @ Tr.double()).float()
+    res = result(T, mask_fix, mask_mov, disp_hr if want_field else None)
     if seg_fixed is not None:
         from .convexAdam_hyper_util import warp_labels_nearest
         sf = f32c(require_device_tensor(seg_fixed, "seg_fixed")).reshape(shape)
@@ -338,7 +371,7 @@ def convex_adam_rigid(img_fixed, imgs_moving, mind_r=3, mind_d=3, grid_sp=6, dis
             raise ValueError("seg_moving must hold labels 1..1023, its maximum is %d" % ml)
         res.tre_before = landmark_tre(sf, sm, ml)                                                          # (:312-319)
         res.tre_deformable = landmark_tre(sf, warp_labels_nearest(sm, disp_hr), ml)                       # (:376-382)
-        res.tre_rigid = landmark_tre(sf, affine_warp(sm[None], T, mode="nearest")[0], ml)                 # (:385-391)
+        setattr(res, tre_name, landmark_tre(sf, affine_warp(sm[None], T, mode="nearest")[0], ml))         # (:385-391)
     return res
 
 

@@ -6,16 +6,9 @@ script runs on the registered field after its Adam stage.
 """
 import torch
 
-from ._lib import check, f32c, lib, ptr, require_device_tensor, stream_ptr, workspace
+from ._lib import _shape, check, f32c, lib, ptr, require_device_tensor, stream_ptr, workspace
 
 _MAX_RHS = 4
-
-
-def _shape(t, name):
-    """The shape of a tensor, read from its metadata only (the checks below answer before any device is touched)."""
-    if not isinstance(t, torch.Tensor):
-        raise TypeError("%s must be a torch.Tensor" % name)
-    return tuple(int(s) for s in t.shape)
 
 
 def _centres(c, name="c"):

@@ -4,6 +4,7 @@ the no-fallback rule hold.  No kernels are launched here."""
 import ctypes as C
 import os
 import re
+import sys
 
 import numpy as np
 import pytest
@@ -11,13 +12,8 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "convexadam_hip.h")
-
-
-def header_functions():
-    src = open(HEADER).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    names = re.findall(r"\b(cvx_[a-z0-9_]+)\s*\(", src)
-    return sorted(set(names))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from abi_headers import header_functions  # noqa: E402
 
 
 @pytest.fixture(scope="module")
@@ -29,7 +25,7 @@ def L():
 
 
 def test_header_declares_expected_entry_points():
-    names = header_functions()
+    names = header_functions(HEADER)
     for must in ("cvx_mindssc_f32", "cvx_avgpool_f32", "cvx_correlate_f32", "cvx_coupled_convex_f32",
                  "cvx_inverse_consistency_f32", "cvx_resize_trilinear_f32", "cvx_adam_run_f32", "cvx_register_pair_f32"):
         assert must in names
@@ -37,10 +33,10 @@ def test_header_declares_expected_entry_points():
 
 def test_library_exports_every_declared_symbol(L):
     from convexadam_amd import _lib
-    for name in header_functions():
+    for name in header_functions(HEADER):
         assert hasattr(L, name), "libconvexadam_hip.so does not export %s" % name
         assert name in _lib.SIGNATURES, "ctypes table lacks %s" % name
-    assert sorted(_lib.SIGNATURES) == header_functions()
+    assert sorted(_lib.SIGNATURES) == header_functions(HEADER)
 
 
 def test_pooled_descriptor_states_its_alignment_contract(L):

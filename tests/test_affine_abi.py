@@ -4,20 +4,15 @@ is refused with a message before anything touches a device (the pointers below a
 import ctypes as C
 import os
 import re
+import sys
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "convexadam_affine.h")
 NAMES = ["cvx_affine_field_f64", "cvx_affine_lts_f32", "cvx_affine_lts_workspace_bytes"]
-
-
-def header_source():
-    return re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-
-
-def header_functions():
-    return sorted(set(re.findall(r"\b(cvx_[a-z0-9_]+)\s*\(", header_source())))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from abi_headers import header_functions, header_source  # noqa: E402
 
 
 @pytest.fixture(scope="module")
@@ -30,12 +25,12 @@ def L():
 
 def test_header_and_table_list_the_same_names(L):
     from convexadam_amd import _affine, _field, _lib, _prep
-    names = header_functions()
+    names = header_functions(HEADER)
     assert names == NAMES and names == sorted(_affine.AFFINE_SIGNATURES)
     for table in (_lib.SIGNATURES, _prep.PREP_SIGNATURES, _field.FIELD_SIGNATURES):
         assert not set(names) & set(table), "the affine entry points have a table of their own"
     main = open(os.path.join(ROOT, "include", "convexadam_hip.h")).read()
-    src = header_source()
+    src = header_source(HEADER)
     for n in names:
         assert hasattr(L, n), "libconvexadam_hip.so does not export %s" % n
         assert n not in main

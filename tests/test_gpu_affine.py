@@ -224,6 +224,23 @@ def test_field_is_bit_identical_to_the_restatement(L, shape, planar, with_u):
             assert same_bits(got, want), (shape, planar, with_u, u64, o64)
 
 
+def test_field_without_u_ignores_its_element_flag(L):
+    """u = NULL with u_f64 = 1, the one pairing of flags the cases above leave out: no displacement is read, whatever the flag says.  A
+    (5, 4, 7) grid: three distinct extents, one partial block"""
+    shape = (5, 4, 7)
+    V = int(np.prod(shape))
+    th = dev(R.THETA)
+    for o64 in (1, 0):
+        want = R.field(R.THETA, shape, None).astype(np.float64 if o64 else np.float32)
+        for planar in (0, 1):
+            out = torch.full((3 * V,), float("nan"), dtype=torch.float64 if o64 else torch.float32, device=DEV)
+            rc = L.cvx_affine_field_f64(p(th), *shape, None, 1, 0, 0, p(out), o64, *((V, 1) if planar else (1, 3)), stream())
+            torch.cuda.synchronize()
+            assert rc == 0, L.cvx_last_error()
+            got = np.moveaxis(out.cpu().numpy().reshape((3,) + shape), 0, -1) if planar else out.cpu().numpy().reshape(shape + (3,))
+            assert same_bits(got, want), (o64, planar)
+
+
 def test_field_on_non_contiguous_views(L):
     """u is the [..., 1:4] part of an (H, W, D, 5) tensor, out the [..., :3] part of an (H, W, D, 4) one: voxel strides 5 and 4; what lies
     between the components' columns is never read (NaN) and never written (a sentinel)"""

@@ -183,6 +183,27 @@ def test_warped_bits_of_apply_convex(cases, n):
     assert np.any(want == 0) and float((want != 0).mean()) > 0.3
 
 
+def test_float32_field_with_a_float64_moving_volume_or_warped_output():
+    """The element types of cvx_field_to_grid_f64 that no case above combines: a float32 field (both layouts) with a float64 moving volume
+    or a float64 warped output.  A (z, y, x) = (5, 4, 7) field grid -- three distinct extents, one partial block -- and a turned moving
+    grid of another spacing, against the restatement."""
+    ident = tuple(np.eye(3).reshape(-1))
+    gr = Grid((7, 4, 5), (1.0, 1.0, 1.0), (0.0, 0.0, 0.0), ident)
+    fg = Grid((4, 4, 3), (2.0, 1.0, 1.5), (0.0, 0.0, 0.0), tuple(G.rot_z(0.1).reshape(-1)))
+    mg = Grid((6, 5, 4), (1.1, 0.8, 1.3), (0.4, -0.3, 0.2), tuple(G.rot_x(0.15).reshape(-1)))
+    field32 = G.smooth_noise((5, 4, 7), 51, amp=1.5, channels=3).astype(F32)
+    mov64 = G.smooth_noise((4, 5, 6), 52) + 0.5
+    carried, _ = G.carry_field(field32.astype(F64), mg, fg, gr)
+    for md, wd in ((F64, F64), (F64, F32), (F32, F64)):
+        mov = mov64.astype(md)
+        want = G.warp(mov, carried)
+        assert 0.3 < float((want != 0).mean()) < 1.0                                         # both sides of apply_convex's rule
+        for f in (field32, np.ascontiguousarray(np.moveaxis(field32, -1, 0))):
+            got_c, got_w = geometry.rescale_displacement_field_device(dev(f), mg, fg, gr, moving=dev(mov), warped_dtype=TORCH_OF[np.dtype(wd)])
+            assert same_bits(got_c.cpu().numpy(), carried), (md, wd, f.shape)
+            assert same_bits(got_w.cpu().numpy(), want.astype(wd)), (md, wd, f.shape)
+
+
 # ---- (d) fused outputs and NaN ------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("n", [1, 2, 3])
 def test_fused_equals_single_outputs_and_nan(cases, n):

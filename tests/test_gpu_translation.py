@@ -210,6 +210,17 @@ def test_seg_mode_on_the_shared_geometries(n):
     check_seg(field.astype(F32), gr, seg, sg, quantize=torch.float16)
 
 
+def test_seg_mode_float32_field_with_a_float32_segmentation():
+    """the one pair of element types no case above combines (a float32 field has met only integer segmentations): a (5, 4, 7) field grid,
+    three distinct extents, and a float32 segmentation on a coarser, shifted grid of its own"""
+    fg = Grid((7, 4, 5), (1.0, 1.0, 1.0), (0.0, 0.0, 0.0), IDENT)
+    sg = Grid((5, 4, 3), (1.5, 1.2, 1.8), (-0.4, -0.3, -0.2), IDENT)
+    field = G.smooth_noise((5, 4, 7), 11, amp=2.0, channels=3).astype(F32)
+    count, mask = check_seg(field, fg, blob((3, 4, 5), 47, 1), sg)
+    assert 0 < count < mask.size
+    check_seg(field, fg, blob((3, 4, 5), 47, 1), sg, quantize=torch.float16)
+
+
 def test_seg_mode_values_exactly_one_half():
     """spacing ratio 2 and a half-voxel offset: every second field voxel lies midway between two segmentation voxels, so a 0 | 1 edge
     interpolates to exactly 0.5 -- which an integer segmentation rounds to 0 (half to even) and a float one keeps above zero"""

@@ -2,17 +2,14 @@
 library exports them, the ABI version is unchanged, and bad arguments are refused before anything touches a device."""
 import ctypes as C
 import os
-import re
+import sys
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "convexadam_prep.h")
-
-
-def header_functions():
-    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(cvx_[a-z0-9_]+)\s*\(", src)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from abi_headers import header_functions  # noqa: E402
 
 
 @pytest.fixture(scope="module")
@@ -25,7 +22,7 @@ def L():
 
 def test_header_and_table_list_the_same_names(L):
     from convexadam_amd import _lib, _prep
-    names = header_functions()
+    names = header_functions(HEADER)
     assert len(names) == 6 and names == sorted(_prep.PREP_SIGNATURES)
     assert not set(names) & set(_lib.SIGNATURES), "the preprocessing entry points have a table of their own"
     main = open(os.path.join(ROOT, "include", "convexadam_hip.h")).read()
