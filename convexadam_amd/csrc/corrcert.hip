@@ -21,7 +21,7 @@
 //                      L2 once per workgroup-step (620 MB per launch; the role kernel of corrfused.hip moves 2 GB through the L1).  The
 //                      staging copies are laid out so that a tile of one channel is ONE contiguous run: lane address = base + 16 tid
 //   raw    (phase 1)   lane = (quad column, row y): conflict-free ds_read_b128 of 1 F + 2 M quads per channel for 4 x B outputs;
-//                      then S.R.S along y with v_fmac_f32_dpp wave_shr / wave_shl (row masks as multipliers), columns >= d zeroed
+//                      then S.R.S along y with DPP wave_shr / wave_shl taps (row ends selected away, not multiplied: NaNs stay where they are), columns >= d zeroed
 //   exch               the y-filtered quads go through LDS once (the transposition to row-major threads)
 //   box    (phase 2)   thread = (row y, quad) row-major: x halo from LDS, S.R.S along x in registers (zero-extended sums + two edge
 //                      corrections), S.R.S along z as two chained running sums, coalesced 16-byte stores of plane q - 2
@@ -241,28 +241,28 @@ __device__ __forceinline__ CCItem cc_decode(const CCKern& g, int b) {
     return it;
 }
 
-// y-direction taps through DPP: acc[j] += a[j](lane -/+ 1) * m.  The sources were written at least two instructions earlier (s_nop 1
-// covers the VALU-write -> DPP-read hazard at the head of a block; inside a block no DPP source is written).
-#define CC_DPP4(ctrl)                                                                                                               \
-    asm("s_nop 1\n\t"                                                                                                              \
-        "v_fmac_f32_dpp %0, %4, %8 " ctrl " row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"                                           \
-        "v_fmac_f32_dpp %1, %5, %8 " ctrl " row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"                                           \
-        "v_fmac_f32_dpp %2, %6, %8 " ctrl " row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"                                           \
-        "v_fmac_f32_dpp %3, %7, %8 " ctrl " row_mask:0xf bank_mask:0xf bound_ctrl:0"                                               \
-        : "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3])                                                                    \
-        : "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "v"(m))
-#define CC_DPP4M(ctrl)                                                                                                              \
-    asm("s_nop 1\n\t"                                                                                                              \
-        "v_fmac_f32_dpp %0, %4, %8 " ctrl " row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"                                           \
-        "v_fmac_f32_dpp %1, %5, %9 " ctrl " row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"                                           \
-        "v_fmac_f32_dpp %2, %6, %10 " ctrl " row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"                                          \
-        "v_fmac_f32_dpp %3, %7, %11 " ctrl " row_mask:0xf bank_mask:0xf bound_ctrl:0"                                              \
-        : "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3])                                                                    \
-        : "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "v"(m[0]), "v"(m[1]), "v"(m[2]), "v"(m[3]))
-__device__ __forceinline__ void cc_tap_up4(float (&acc)[4], const float (&a)[4], const float (&m)[4]) { CC_DPP4M("wave_shr:1"); }
-__device__ __forceinline__ void cc_tap_dn4(float (&acc)[4], const float (&a)[4], const float (&m)[4]) { CC_DPP4M("wave_shl:1"); }
-__device__ __forceinline__ void cc_tap_up(float (&acc)[4], const float (&a)[4], float m) { CC_DPP4("wave_shr:1"); }
-__device__ __forceinline__ void cc_tap_dn(float (&acc)[4], const float (&a)[4], float m) { CC_DPP4("wave_shl:1"); }
+// y-direction taps through DPP: acc[j] += a[j](lane -/+ 1) where `on`.  A tap that is off is SELECTED away, never multiplied by zero: the
+// neighbouring lane of a row end belongs to another column (or to no voxel at all), and a NaN feature there -- NaNs are inside the input
+// contract -- would pass 0 x NaN = NaN into a sum it has no part in.  (The first version multiplied by 0 / 1 masks in v_fmac_f32_dpp: one
+// instruction per tap instead of two, and NaNs of the moving features in the first or last row of a plane spread into the next column.)
+__device__ __forceinline__ float cc_lane_up(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x138, 0xf, 0xf, true)); }   // wave_shr:1 (lane 0: 0)
+__device__ __forceinline__ float cc_lane_dn(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x130, 0xf, 0xf, true)); }   // wave_shl:1 (lane 63: 0)
+__device__ __forceinline__ void cc_tap_up4(float (&acc)[4], const float (&a)[4], const bool (&on)[4]) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { const float v = cc_lane_up(a[j]); acc[j] += on[j] ? v : 0.0f; }
+}
+__device__ __forceinline__ void cc_tap_dn4(float (&acc)[4], const float (&a)[4], const bool (&on)[4]) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { const float v = cc_lane_dn(a[j]); acc[j] += on[j] ? v : 0.0f; }
+}
+__device__ __forceinline__ void cc_tap_up(float (&acc)[4], const float (&a)[4], bool on) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { const float v = cc_lane_up(a[j]); acc[j] += on ? v : 0.0f; }
+}
+__device__ __forceinline__ void cc_tap_dn(float (&acc)[4], const float (&a)[4], bool on) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { const float v = cc_lane_dn(a[j]); acc[j] += on ? v : 0.0f; }
+}
 
 // workgroup barrier of this kernel: the waits are explicit (a __syncthreads() fence would drain the LDS-DMA queue again)
 #ifdef CVX_RACE_JITTER
@@ -553,12 +553,12 @@ __device__ __forceinline__ void cc_run(const CCKern& g, const CCCtx& c, const CC
             }
             // S.R.S along y; columns >= d become exact zeros (the x pass zero-extends its input)
             const int yo = cc_opaque(y1), qo = cc_opaque(q1), xwo = cc_opaque(xw);
-            const float mu = yo > 0 ? 1.0f : 0.0f, md = yo < w - 1 ? 1.0f : 0.0f;
-            // column masks: folded into the second sum's taps where the registers allow it (sets of at most four shifts), else one more product
+            const bool mu = yo > 0, md = yo < w - 1;
+            // column masks: folded into the second sum's taps where the registers allow it (sets of at most four shifts), else one more select
             constexpr bool FOLD = B <= 4;
-            float mc[4], muc[FOLD ? 4 : 1], mdc[FOLD ? 4 : 1];
+            bool mc[4], muc[FOLD ? 4 : 1], mdc[FOLD ? 4 : 1];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) { mc[j] = (4 * qo + j < d) ? 1.0f : 0.0f; if (FOLD) { muc[j] = mu * mc[j]; mdc[j] = md * mc[j]; } }
+            for (int j = 0; j < 4; ++j) { mc[j] = 4 * qo + j < d; if (FOLD) { muc[j] = mu && mc[j]; mdc[j] = md && mc[j]; } }
 #pragma unroll
             for (int k = 0; k < B; ++k) {
                 float t[4], u[4];
@@ -568,16 +568,16 @@ __device__ __forceinline__ void cc_run(const CCKern& g, const CCCtx& c, const CC
                 cc_tap_dn(t, acc[k], md);
                 if (FOLD) {
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) u[j] = t[j] * mc[j];
-                    cc_tap_up4(u, t, reinterpret_cast<const float (&)[4]>(muc));
-                    cc_tap_dn4(u, t, reinterpret_cast<const float (&)[4]>(mdc));
+                    for (int j = 0; j < 4; ++j) u[j] = mc[j] ? t[j] : 0.0f;
+                    cc_tap_up4(u, t, reinterpret_cast<const bool (&)[4]>(muc));
+                    cc_tap_dn4(u, t, reinterpret_cast<const bool (&)[4]>(mdc));
                 } else {
 #pragma unroll
                     for (int j = 0; j < 4; ++j) u[j] = t[j];
                     cc_tap_up(u, t, mu);
                     cc_tap_dn(u, t, md);
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) u[j] *= mc[j];
+                    for (int j = 0; j < 4; ++j) u[j] = mc[j] ? u[j] : 0.0f;
                 }
                 if (act1) lds_store4(c.exch + k * g.exq * 4 + xwo, f32x4{u[0], u[1], u[2], u[3]});
                 __builtin_amdgcn_sched_barrier(0);          // one shift at a time: the scheduler must not interleave all B (register pressure)
