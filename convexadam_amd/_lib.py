@@ -1,4 +1,8 @@
-"""ctypes binding of libconvexadam_hip.so (include/convexadam_hip.h).
+"""ctypes binding of libconvexadam_hip.so and the one call path into it.
+
+One table per public header: SIGNATURES (include/convexadam_hip.h), PREP_SIGNATURES (convexadam_prep.h), FIELD_SIGNATURES
+(convexadam_field.h), AFFINE_SIGNATURES (convexadam_affine.h); lib() types all four when it loads the library.  Every entry point that
+takes a stream is entered through call(), every scratch buffer comes from scratch().
 
 The HIP library IS the product: there is no CPU or PyTorch fallback.  If the shared object is
 missing (not built) or an operator is called with tensors that do not live on a HIP device, the call
@@ -15,6 +19,7 @@ LIB_PATH = os.environ.get("CONVEXADAM_HIP_LIB") or os.path.join(_HERE, "csrc", "
 
 ABI_VERSION = 2          # CVX_ABI_VERSION of include/convexadam_hip.h this binding was written against
 CVX_OK, CVX_ERR_INVALID_ARG, CVX_ERR_WORKSPACE, CVX_ERR_LAUNCH, CVX_ERR_UNSUPPORTED = 0, -1, -2, -3, -4
+CVX_PREP_CLAMP, CVX_PREP_POSITIVE = 1, 2          # flags of cvx_prep_stats_f32 (include/convexadam_prep.h)
 
 
 class CvxError(RuntimeError):
@@ -48,7 +53,7 @@ class StageParams(C.Structure):
                 ("ic_iters", C.c_int), ("H", C.c_int), ("W", C.c_int), ("D", C.c_int), ("ctx", C.c_void_p), ("reserved_", C.c_int * 4)]
 
 
-_vp, _i, _f, _sz, _i64 = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_int64
+_vp, _i, _f, _sz, _i64, _ll, _d = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_int64, C.c_longlong, C.c_double
 
 # the arguments every cvx_adam_run_* entry point starts with (F2 .. snapshots); a smoother / mode, then workspace, its size and the stream follow
 _ADAM_HEAD = [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]
@@ -175,22 +180,61 @@ SIGNATURES = {
     "cvx_ranksum_better_f64": (_i, [_vp, _vp, C.c_double, C.c_double, _i, _i, _i, _i, _vp, _vp, _vp]),
 }
 
+# include/convexadam_prep.h (tests/test_abi.py compares each side header with its own table)
+PREP_SIGNATURES = {
+    "cvx_prep_stats_workspace_bytes": (_sz, [_ll]),
+    "cvx_prep_stats_f32": (_i, [_vp, _ll, _i, _f, _f, _i, _f, _f, _vp, _vp, _vp, _sz, _vp]),
+    "cvx_prep_normalise_f32": (_i, [_vp, _ll, _vp, C.POINTER(C.c_float), _i, _vp, _vp]),
+    "cvx_prep_nonzero_mask_workspace_bytes": (_sz, [_i, _i, _i]),
+    "cvx_prep_nonzero_mask_u8": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, C.POINTER(C.c_int), _vp, _sz, _vp]),
+    "cvx_prep_mask_bbox_i32": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
+}
+
+_FIELD = [_vp, _i, _i64, _i64]          # a field operand: pointer, elements are double, component stride, voxel stride
+
+# include/convexadam_field.h
+FIELD_SIGNATURES = {
+    "cvx_field_invert_f64": (_i, _FIELD + [_i, _i, _i, _i, _d] + _FIELD + [_vp, _vp, _vp, _vp]),
+    "cvx_field_compose_f64": (_i, _FIELD + _FIELD + [_i, _i, _i] + _FIELD + [_vp]),
+}
+
+# include/convexadam_affine.h
+AFFINE_SIGNATURES = {
+    "cvx_affine_lts_workspace_bytes": (_sz, [_i64]),
+    "cvx_affine_lts_f32": (_i, [_vp, _i, _vp, _i, _i64, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "cvx_affine_field_f64": (_i, [_vp, _i, _i, _i] + _FIELD + _FIELD + [_vp]),
+}
+
+_REBUILD = "rebuild with `python -m convexadam_amd.csrc.build`"
 _lib = None
 _lock = threading.Lock()
 
 
 def bind(L, table):
-    """Types the entry points of a name -> (restype, argtypes) table on the handle L (raises if one is missing: there is no fallback).
-    Setting the same types twice is harmless, so the cached lib() of _prep.py, _field.py and _affine.py need no lock."""
+    """Types the entry points of a name -> (restype, argtypes) table on the handle L; a handle that lacks one is refused by name (there is
+    no fallback)."""
     for name, (res, args) in table.items():
-        fn = getattr(L, name)
+        try:
+            fn = getattr(L, name)
+        except AttributeError:
+            raise RuntimeError("%s lacks the entry point %s: %s" % (LIB_PATH, name, _REBUILD)) from None
         fn.restype = res
         fn.argtypes = args
     return L
 
 
+def _typed(L):
+    """The handle L with the entry points of all four headers typed and its ABI version checked."""
+    for table in (SIGNATURES, PREP_SIGNATURES, FIELD_SIGNATURES, AFFINE_SIGNATURES):
+        bind(L, table)
+    if L.cvx_version() != ABI_VERSION:
+        raise RuntimeError("%s reports ABI version %d, this binding needs %d (struct layouts differ): %s"
+                           % (LIB_PATH, L.cvx_version(), ABI_VERSION, _REBUILD))
+    return L
+
+
 def lib():
-    """Loads the HIP library (raises if it has not been built -- never falls back)."""
+    """Loads the HIP library (raises if it has not been built or lacks a declared entry point -- never falls back)."""
     global _lib
     if _lib is None:
         with _lock:
@@ -198,17 +242,17 @@ def lib():
                 if not os.path.exists(LIB_PATH):
                     raise RuntimeError("%s not found: build it with `python -m convexadam_amd.csrc.build` "
                                        "(there is no CPU fallback)" % LIB_PATH)
-                L = bind(C.CDLL(LIB_PATH), SIGNATURES)
-                if L.cvx_version() != ABI_VERSION:
-                    raise RuntimeError("%s reports ABI version %d, this binding needs %d (struct layouts differ): rebuild with "
-                                       "`python -m convexadam_amd.csrc.build`" % (LIB_PATH, L.cvx_version(), ABI_VERSION))
-                _lib = L
+                _lib = _typed(C.CDLL(LIB_PATH))
     return _lib
+
+
+def _last_error():
+    return lib().cvx_last_error().decode("utf-8", "replace")
 
 
 def check(rc):
     if rc != CVX_OK:
-        raise CvxError(rc, lib().cvx_last_error().decode("utf-8", "replace"))
+        raise CvxError(rc, _last_error())
 
 
 def require_device_tensor(t, name):
@@ -297,7 +341,7 @@ def workspace(nbytes, device):
     ws = getattr(_tls, "workspaces", None)
     if ws is None:
         ws = _tls.workspaces = {}
-    key = (str(device), torch.cuda.current_stream(device).cuda_stream)
+    key = (str(device), stream_ptr(device).value or 0)          # (the stream call() hands to the library; the null stream is 0)
     buf = ws.get(key)
     if buf is None or buf.numel() < nbytes:
         ws[key] = buf = torch.empty(int(nbytes * 1.05) + 4096, dtype=torch.uint8, device=device)
@@ -308,3 +352,34 @@ def release_workspaces():
     """Drops the calling thread's scratch buffers."""
     if getattr(_tls, "workspaces", None):
         _tls.workspaces.clear()
+
+
+def scratch(dev, query_name, *query_args, required=False, otherwise="", size=None):
+    """(pointer, nbytes) of the calling thread's scratch buffer for the current stream of `dev`, sized by the library's query
+    `query_name(*query_args)`: the only caller of a *_workspace_bytes / *_scratch_bytes query on the way to a launch and the only caller
+    of workspace().  nbytes is the query's value, unchanged; the pointer is never null (a query that answers 0 still gets a buffer), so
+    a launcher that refuses a size of 0 refuses it for the size and nothing else.  required=True: 0 means that the library refused the
+    query's arguments -> CvxError(CVX_ERR_INVALID_ARG) with cvx_last_error's text, or `otherwise` where that is empty.  The pair goes
+    directly in front of the stream in most entry points: call(dev, name, ..., *scratch(dev, query, ...)).  size=f is for the one
+    entry point whose workspace the library has no query for (cvx_register_pairs_f32: n_streams slots of the single pair's size): nbytes
+    is then f(the query's value), the caller's own arithmetic."""
+    nbytes = getattr(lib(), query_name)(*query_args)
+    if required and nbytes == 0:
+        raise CvxError(CVX_ERR_INVALID_ARG, _last_error() or otherwise)
+    if size is not None:
+        nbytes = size(nbytes)
+    return ptr(workspace(nbytes, dev)), nbytes
+
+
+def call(dev, name, *args):
+    """The one way into an entry point that takes a stream (all of them take it last): runs lib().name(*args, current stream of `dev`)
+    with `dev` as the current device and raises CvxError on a status other than CVX_OK.  `dev` is the device the operands live on, never
+    simply the current one; where it already is the current one (or names no index) the guard is skipped.  Adds no synchronisation and
+    no allocation.  The host-only entry points (*_host, cvx_const_div_*, the option, table and profiling setters, cvx_last_*) take no
+    stream and are called on lib() directly."""
+    fn = getattr(lib(), name)
+    index = torch.device(dev).index
+    if index is None or index == torch.cuda.current_device():
+        return check(fn(*args, stream_ptr(dev)))
+    with torch.cuda.device(index):
+        check(fn(*args, stream_ptr(dev)))

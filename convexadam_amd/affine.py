@@ -14,8 +14,7 @@ rigid.py requires them; there is no CPU path.
 """
 import torch
 
-from . import _affine
-from ._lib import _shape, check, f32c, field_operand_from, ptr, require_device_tensor, stream_ptr
+from ._lib import _shape, call, f32c, field_operand_from, ptr, require_device_tensor
 from .rigid import _field_samples, _fit, _point_pair, _register, _trimmed_iters, _volume, affine_warp
 
 MIN_CELLS = 8          # a trimmed affine fit works on n // 2 >= 4 points
@@ -26,14 +25,14 @@ def find_affine_3d(x, y):
     without its restriction to rotations.  x, y: (N, k >= 3) device tensors, N >= 4; columns beyond the third are ignored.  Raises
     CvxError on coplanar points (a singular system) or a non-finite coordinate."""
     _point_pair(x, y, ("x", "y"), 4)
-    return _fit(_affine.lib, "cvx_affine_lts", x[:, :3], y[:, :3], False, 1, 0).t().contiguous()
+    return _fit("cvx_affine_lts", x[:, :3], y[:, :3], False, 1, 0).t().contiguous()
 
 
 def _trimmed(fixed_pts, moving_pts, iter, normal, return_inliers):
     n = _point_pair(fixed_pts, moving_pts, ("fixed_pts", "moving_pts"), 4, 4)
     if _trimmed_iters(iter) > 1 and n < MIN_CELLS:
         raise ValueError("a trimmed fit needs N >= %d points, got %d" % (MIN_CELLS, n))
-    return _fit(_affine.lib, "cvx_affine_lts", fixed_pts, moving_pts, bool(return_inliers), int(iter), normal)
+    return _fit("cvx_affine_lts", fixed_pts, moving_pts, bool(return_inliers), int(iter), normal)
 
 
 def least_trimmed_affine(fixed_pts, moving_pts, iter=5, return_inliers=False):
@@ -126,9 +125,7 @@ def affine_to_field(T, shape, field=None):
             raise ValueError("affine_to_field: field is %s on %s, shape %s and T on %s" % (ushape, u.device, (H, W, D), dev))
         out = torch.empty(u.shape, dtype=torch.float64, device=dev)
         ocs, ovs = cs, vs
-    with torch.cuda.device(dev):
-        check(_affine.lib().cvx_affine_field_f64(ptr(th), H, W, D, ptr(u), u64, cs, vs, ptr(out), 1, ocs, ovs,
-                                                 stream_ptr(dev)))
+    call(dev, "cvx_affine_field_f64", ptr(th), H, W, D, ptr(u), u64, cs, vs, ptr(out), 1, ocs, ovs)
     return out
 
 

@@ -13,7 +13,7 @@ and built-in images both steps are one kernel launch (geometry.rescale_displacem
 import numpy as np
 import torch
 
-from ._lib import check, lib, ptr, stream_ptr
+from ._lib import call, ptr
 from .convex_adam_utils import rescale_displacement_field, validate_image
 
 
@@ -30,8 +30,7 @@ def apply_convex(disp, moving, device=None) -> np.ndarray:
     d = disp_t.to(dev, torch.float64).contiguous()
     H, W, D = [int(v) for v in m.shape]
     out = torch.empty_like(m)
-    with torch.cuda.device(dev):
-        check(lib().cvx_map_coordinates_linear_f64(ptr(m), ptr(d), H, W, D, ptr(out), stream_ptr(dev)))
+    call(dev, "cvx_map_coordinates_linear_f64", ptr(m), ptr(d), H, W, D, ptr(out))
     if not out_dtype.is_floating_point:
         out = torch.trunc(out + torch.where(out > 0, 0.5, -0.5))   # scipy's integer outputs: (type)(t > 0 ? t + 0.5 : t - 0.5), ni_interpolation.c
     return out.to(out_dtype).cpu().numpy()

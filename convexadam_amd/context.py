@@ -14,7 +14,7 @@ import threading
 import numpy as np
 import torch
 
-from ._lib import check, lib, ptr, stream_ptr
+from ._lib import call, check, lib, ptr
 
 
 class Context:
@@ -42,8 +42,7 @@ class Context:
             return self
         t = _as_device_u8(codes, device)
         assert t.numel() == 6 * 1024 * 1024, "sqrt table: 2 bits x (2^24 + 2^23) classes = 6 MiB"
-        with torch.cuda.device(t.device):
-            check(lib().cvx_context_set_adam_sqrt_table(self._h, ptr(t), stream_ptr(t.device)))
+        call(t.device, "cvx_context_set_adam_sqrt_table", self._h, ptr(t))
         return self
 
     def set_mind_exp_table(self, table=None, first=0, count=0, device="cuda"):
@@ -52,8 +51,7 @@ class Context:
             return self
         t = _as_device_u8(table, device)
         assert t.numel() * 4 >= count > 0
-        with torch.cuda.device(t.device):
-            check(lib().cvx_context_set_mind_exp_table(self._h, ptr(t), int(first), int(count), stream_ptr(t.device)))
+        call(t.device, "cvx_context_set_mind_exp_table", self._h, ptr(t), int(first), int(count))
         return self
 
     # -- binding ------------------------------------------------------------------------------------------

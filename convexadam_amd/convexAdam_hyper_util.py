@@ -27,7 +27,7 @@ import os
 import numpy as np
 import torch
 
-from ._lib import Smoother, check, f32c, lib, ptr, require_device_tensor, stream_ptr, workspace
+from ._lib import Smoother, call, f32c, lib, ptr, require_device_tensor, scratch
 from .convex_adam_utils import coupled_convex, correlate, gpu_usage, inverse_consistency  # noqa: F401  (same operators)
 from .convex_adam_utils import MINDSSC as _MINDSSC
 from .convex_adam_MIND import extract_features as _extract_features
@@ -64,10 +64,8 @@ def _apply(x, spec, backward):
     _, Cn, H, W, D = [int(s) for s in x.shape]
     a = f32c(x)
     out = torch.empty_like(a)
-    nws = lib().cvx_smooth_workspace_bytes(Cn, H, W, D)
-    ws = workspace(nws, a.device)
-    with torch.cuda.device(a.device):
-        check(lib().cvx_smooth_f32(ptr(a), Cn, H, W, D, C.byref(spec), 1 if backward else 0, ptr(out), ptr(ws), nws, stream_ptr(a.device)))
+    call(a.device, "cvx_smooth_f32", ptr(a), Cn, H, W, D, C.byref(spec), 1 if backward else 0, ptr(out),
+         *scratch(a.device, "cvx_smooth_workspace_bytes", Cn, H, W, D))
     return out
 
 
@@ -143,8 +141,7 @@ def jacobian_determinant_3d(dense_flow, convert1=True):
     out = torch.empty((max(H - 4, 0), max(W - 4, 0), max(D - 4, 0)), dtype=torch.float32, device=x.device)
     if out.numel() == 0:                         # an extent of at most 4 voxels: the slice [2:-2] of the reference (:103) is empty
         return out
-    with torch.cuda.device(x.device):
-        check(lib().cvx_jacobian_det_f32(ptr(x), H, W, D, 1 if convert1 else 0, ptr(out), stream_ptr(x.device)))
+    call(x.device, "cvx_jacobian_det_f32", ptr(x), H, W, D, 1 if convert1 else 0, ptr(out))
     return out
 
 
@@ -154,8 +151,7 @@ def jacobian_log_std_and_folding(jac_det):
     j = f32c(require_device_tensor(jac_det, "jac_det")).reshape(-1)
     n = int(j.numel())
     acc = torch.empty(3, dtype=torch.float64, device=j.device)
-    with torch.cuda.device(j.device):
-        check(lib().cvx_jacobian_stats_f64(ptr(j), n, ptr(acc), stream_ptr(j.device)))
+    call(j.device, "cvx_jacobian_stats_f64", ptr(j), n, ptr(acc))
     s, s2, neg = [float(v) for v in acc.cpu()]
     if n == 1:
         return float("nan"), neg / n
@@ -174,8 +170,7 @@ def warp_labels_nearest(seg_moving, disp_hr):
         raise ValueError("warp_labels_nearest: disp_hr must be (1,3,H,W,D) matching the label map")
     bh, bw, bd = _base_tables(H, W, D, seg.device)
     out = torch.empty((H, W, D), dtype=torch.float32, device=seg.device)
-    with torch.cuda.device(seg.device):
-        check(lib().cvx_warp_labels_nearest_f32(ptr(seg), ptr(d), H, W, D, ptr(bh), ptr(bw), ptr(bd), ptr(out), stream_ptr(seg.device)))
+    call(seg.device, "cvx_warp_labels_nearest_f32", ptr(seg), ptr(d), H, W, D, ptr(bh), ptr(bw), ptr(bd), ptr(out))
     return out
 
 
@@ -187,8 +182,7 @@ def label_overlap_counts(a, b, max_label):
     if a.numel() != b.numel():
         raise ValueError("label maps differ in size")
     counts = torch.empty((3, int(max_label)), dtype=torch.int64, device=a.device)
-    with torch.cuda.device(a.device):
-        check(lib().cvx_label_overlap_i64(ptr(a), ptr(b), int(a.numel()), int(max_label), ptr(counts), stream_ptr(a.device)))
+    call(a.device, "cvx_label_overlap_i64", ptr(a), ptr(b), int(a.numel()), int(max_label), ptr(counts))
     return counts.cpu().numpy()
 
 
@@ -262,12 +256,8 @@ def edt_squared(obj):
         raise ValueError("edt_squared: (H,W,D) or (B,H,W,D) tensor expected")
     B = int(o.shape[0]) if o.dim() == 4 else 1
     H, W, D = [int(v) for v in o.shape[-3:]]
-    L = lib()
     out = torch.empty(tuple(o.shape), dtype=torch.int32, device=o.device)
-    nws = L.cvx_edt_squared_workspace_bytes(B, H, W, D)
-    ws = workspace(nws, o.device)
-    with torch.cuda.device(o.device):
-        check(L.cvx_edt_squared_i32(ptr(o), B, H, W, D, ptr(out), ptr(ws), nws, stream_ptr(o.device)))
+    call(o.device, "cvx_edt_squared_i32", ptr(o), B, H, W, D, ptr(out), *scratch(o.device, "cvx_edt_squared_workspace_bytes", B, H, W, D))
     return out
 
 
@@ -312,9 +302,7 @@ def cupy_hd95(fixed, moving, num_labels, precision=1, fixed_cache=None, method=N
         raise RuntimeError("cupy_hd95: Input and output sizes should be greater than 0 (%dx%dx%d at precision %g)" % (H, W, D, prec))
     nbins = (Ho - 1) ** 2 + (Wo - 1) ** 2 + (Do - 1) ** 2 + 2
     nl = int(num_labels)
-    L = lib()
     dev = fx.device
-    sp = stream_ptr(dev)
     n = Ho * Wo * Do
 
     def transforms(seg, labs):
@@ -324,22 +312,20 @@ def cupy_hd95(fixed, moving, num_labels, precision=1, fixed_cache=None, method=N
             for g0 in range(0, len(labs), 64):
                 part = labs[g0:g0 + 64]
                 arr = (C.c_int * len(part))(*part)
-                nws = L.cvx_edt_squared_workspace_bytes(2 * len(part), Ho, Wo, Do)
-                ws = workspace(nws, dev)
-                check(L.cvx_edt_squared_labels_i32(ptr(seg), H, W, D, C.cast(arr, C.c_void_p), len(part), ptr(out[g0:g0 + len(part)]), ptr(ws), nws, sp))
+                call(dev, "cvx_edt_squared_labels_i32", ptr(seg), H, W, D, C.cast(arr, C.c_void_p), len(part), ptr(out[g0:g0 + len(part)]),
+                     *scratch(dev, "cvx_edt_squared_workspace_bytes", 2 * len(part), Ho, Wo, Do))
             return out
         group = max(1, min(len(labs), int((4 << 30) // (40 * n))))
         obj = torch.empty((group, 2, Ho, Wo, Do), dtype=torch.float32, device=dev)
-        nws = L.cvx_edt_squared_workspace_bytes(2 * group, Ho, Wo, Do)
-        ws = workspace(nws, dev)
+        ws = scratch(dev, "cvx_edt_squared_workspace_bytes", 2 * group, Ho, Wo, Do)
         for g0 in range(0, len(labs), group):
             part = labs[g0:g0 + group]
             for i, lab in enumerate(part):
                 if p and p <= 8:
-                    check(L.cvx_label_mask_f32(ptr(seg), H, W, D, lab, p, ptr(obj[i, 0]), ptr(obj[i, 1]), None, sp))
+                    call(dev, "cvx_label_mask_f32", ptr(seg), H, W, D, lab, p, ptr(obj[i, 0]), ptr(obj[i, 1]), None)
                 else:
-                    check(L.cvx_label_mask_scaled_f32(ptr(seg), H, W, D, lab, Ho, Wo, Do, float(np.float32(1.0 / prec)), ptr(obj[i, 0]), ptr(obj[i, 1]), None, sp))
-            check(L.cvx_edt_squared_i32(ptr(obj), 2 * len(part), Ho, Wo, Do, ptr(out[g0:g0 + len(part)]), ptr(ws), nws, sp))
+                    call(dev, "cvx_label_mask_scaled_f32", ptr(seg), H, W, D, lab, Ho, Wo, Do, float(np.float32(1.0 / prec)), ptr(obj[i, 0]), ptr(obj[i, 1]), None)
+            call(dev, "cvx_edt_squared_i32", ptr(obj), 2 * len(part), Ho, Wo, Do, ptr(out[g0:g0 + len(part)]), *ws)
         return out
 
     if method is None:
@@ -349,103 +335,100 @@ def cupy_hd95(fixed, moving, num_labels, precision=1, fixed_cache=None, method=N
     if method == "surface":
         if not (p == 1 and 1 <= nl <= 255 and H <= 2047 and W <= 2047):
             raise NotImplementedError("cupy_hd95: method 'surface' needs precision 1, 1 .. 255 labels and H, W <= 2047")
-        with torch.cuda.device(dev):
-            # label range (F.one_hot, :33) and presence in one pass: voxel counts of the integer values 0 .. num_labels in both maps
-            cnt = label_overlap_counts(fx, mv, nl + 1) if counts is None else counts
-            if cnt.shape != (3, nl + 1):
-                raise ValueError("cupy_hd95: counts must be label_overlap_counts(fixed, moving, num_labels + 1)")
-            if int(cnt[0].sum()) != n or int(cnt[1].sum()) != n:
-                raise RuntimeError("cupy_hd95: class values must be in 0 .. num_labels (F.one_hot, :33)")
-            present = [i for i in range(1, nl + 1) if cnt[0, i] > 0 and cnt[1, i] > 0]
-            res = None
-            if present:
-                nwords = int(L.cvx_label_bits_bytes(H, W, D, nl)) // 8
-
-                def planes(seg):
-                    b = torch.empty(nwords, dtype=torch.int64, device=dev)
-                    check(L.cvx_label_bits_u64(ptr(seg), H, W, D, nl, ptr(b), sp))
-                    return b
-
-                if fixed_cache is not None:
-                    key = ("bits", nl)
-                    if key not in fixed_cache:
-                        fixed_cache[key] = planes(fx)
-                    bits_f = fixed_cache[key]
-                else:
-                    bits_f = planes(fx)
-                bits_m = planes(mv)
-                hist = torch.zeros((nl, 2, nbins), dtype=torch.int64, device=dev)
-                tail = torch.zeros(nl * 2 * 3 + nl, dtype=torch.int64, device=dev)       # out3 [nl][2][3] | overflow [nl][2] int32
-                out3, flag = tail[:nl * 6], tail[nl * 6:].view(torch.int32)
-                act = [0, 0, 0, 0]
-                for lab in present:
-                    act[lab >> 6] |= 1 << (lab & 63)
-                act4 = (C.c_uint64 * 4)(*act)
-                # k = 0: dist1[surf2] (surface of the moving map against the fixed planes), k = 1: dist2[surf1] (:48)
-                # (HD95_SURFACE_KERNEL = "bits", the default: both maps as bit planes, 64 voxels per thread; "voxels": one lane per voxel of
-                # the label map -- the round-4 kernel, same counts)
-                use_bits = HD95_SURFACE_KERNEL == "bits" and nl * H * W * ((D + 63) // 64) < (1 << 32)       # (the word lists index 32 bits)
-                nws = int(L.cvx_surface_distance_hist_bits_workspace_bytes(H, W, D, nl)) if use_bits else 0
-                ws = workspace(nws, dev) if nws else None
-                for k, (seg_b, bits_b, bits_a) in enumerate(((mv, bits_m, bits_f), (fx, bits_f, bits_m))):
-                    if use_bits:
-                        check(L.cvx_surface_distance_hist_bits_i64(ptr(bits_b), ptr(bits_a), H, W, D, nl, C.cast(act4, C.c_void_p), nbins,
-                                                                   C.c_void_p(hist.data_ptr() + 8 * k * nbins), 2 * nbins,
-                                                                   C.c_void_p(flag.data_ptr() + 4 * k), 2, int(HD95_SURFACE_MAX_RADIUS), ptr(ws), nws, sp))
-                    else:
-                        check(L.cvx_surface_distance_hist_i64(ptr(seg_b), ptr(bits_a), H, W, D, nl, C.cast(act4, C.c_void_p), nbins,
-                                                              C.c_void_p(hist.data_ptr() + 8 * k * nbins), 2 * nbins,
-                                                              C.c_void_p(flag.data_ptr() + 4 * k), 2, int(HD95_SURFACE_MAX_RADIUS), sp))
-                quant = float(np.true_divide(95, np.float32(100)))               # numpy: q / float32(100) for float32 data
-                check(L.cvx_hist_percentile_neighbours_batch_i64(ptr(hist), nbins, 2 * nl, quant, ptr(out3), sp))
-                host = tail.cpu().numpy()
-                flags = host[nl * 6:].view(np.int32)[[2 * (lab - 1) + k for lab in present for k in range(2)]]
-                if np.any(flags == 2):               # a surface voxel farther than HD95_SURFACE_MAX_RADIUS rows from its target: the ring
-                    # the search would crawl: the transforms take over.  The fixed map's transforms are NOT kept in the caller's cache here
-                    # (715 MB per pair at 160x192x224, for a case that should be rare)
-                    return cupy_hd95(fixed, moving, num_labels, precision, None, method="edt", counts=cnt)
-                if np.any(flags != 0):
-                    raise RuntimeError("cupy_hd95: squared distance exceeds the histogram range")
-                res = host[:nl * 6].reshape(nl, 2, 3)[[lab - 1 for lab in present]]
-        return _hd95_from_order_stats(res, present, nl, precision, dev)
-    with torch.cuda.device(dev):
-        # label range (F.one_hot, :33) and presence in one pass: voxel counts of labels 0 .. num_labels in both maps
+        # label range (F.one_hot, :33) and presence in one pass: voxel counts of the integer values 0 .. num_labels in both maps
         cnt = label_overlap_counts(fx, mv, nl + 1) if counts is None else counts
         if cnt.shape != (3, nl + 1):
             raise ValueError("cupy_hd95: counts must be label_overlap_counts(fixed, moving, num_labels + 1)")
-        if int(cnt[0].sum()) != int(fx.numel()) or int(cnt[1].sum()) != int(fx.numel()):
+        if int(cnt[0].sum()) != n or int(cnt[1].sum()) != n:
             raise RuntimeError("cupy_hd95: class values must be in 0 .. num_labels (F.one_hot, :33)")
         present = [i for i in range(1, nl + 1) if cnt[0, i] > 0 and cnt[1, i] > 0]
+        res = None
         if present:
+            nwords = int(lib().cvx_label_bits_bytes(H, W, D, nl)) // 8
+
+            def planes(seg):
+                b = torch.empty(nwords, dtype=torch.int64, device=dev)
+                call(dev, "cvx_label_bits_u64", ptr(seg), H, W, D, nl, ptr(b))
+                return b
+
             if fixed_cache is not None:
-                key = ("edt", prec, nl)
+                key = ("bits", nl)
                 if key not in fixed_cache:
-                    labs_f = [i for i in range(1, nl + 1) if cnt[0, i] > 0]
-                    fixed_cache[key] = (labs_f, transforms(fx, labs_f))
-                labs_f, dist_f_all = fixed_cache[key]
-                dist_f = [dist_f_all[labs_f.index(lab)] for lab in present]
+                    fixed_cache[key] = planes(fx)
+                bits_f = fixed_cache[key]
             else:
-                dist_f_all = transforms(fx, present)
-                dist_f = [dist_f_all[j] for j in range(len(present))]
-            dist_m = transforms(mv, present)
-            hist = torch.empty((2 * len(present), nbins), dtype=torch.int64, device=dev)
-            flag = torch.zeros(2 * len(present), dtype=torch.int32, device=dev)
-            out3 = torch.empty((len(present), 2, 3), dtype=torch.int64, device=dev)
+                bits_f = planes(fx)
+            bits_m = planes(mv)
+            hist = torch.zeros((nl, 2, nbins), dtype=torch.int64, device=dev)
+            tail = torch.zeros(nl * 2 * 3 + nl, dtype=torch.int64, device=dev)       # out3 [nl][2][3] | overflow [nl][2] int32
+            out3, flag = tail[:nl * 6], tail[nl * 6:].view(torch.int32)
+            act = [0, 0, 0, 0]
+            for lab in present:
+                act[lab >> 6] |= 1 << (lab & 63)
+            act4 = (C.c_uint64 * 4)(*act)
+            # k = 0: dist1[surf2] (surface of the moving map against the fixed planes), k = 1: dist2[surf1] (:48)
+            # (HD95_SURFACE_KERNEL = "bits", the default: both maps as bit planes, 64 voxels per thread; "voxels": one lane per voxel of
+            # the label map -- the round-4 kernel, same counts)
+            use_bits = HD95_SURFACE_KERNEL == "bits" and nl * H * W * ((D + 63) // 64) < (1 << 32)       # (the word lists index 32 bits)
+            ws = scratch(dev, "cvx_surface_distance_hist_bits_workspace_bytes", H, W, D, nl) if use_bits else None
+            for k, (seg_b, bits_b, bits_a) in enumerate(((mv, bits_m, bits_f), (fx, bits_f, bits_m))):
+                if use_bits:
+                    call(dev, "cvx_surface_distance_hist_bits_i64", ptr(bits_b), ptr(bits_a), H, W, D, nl, C.cast(act4, C.c_void_p), nbins,
+                         C.c_void_p(hist.data_ptr() + 8 * k * nbins), 2 * nbins, C.c_void_p(flag.data_ptr() + 4 * k), 2,
+                         int(HD95_SURFACE_MAX_RADIUS), *ws)
+                else:
+                    call(dev, "cvx_surface_distance_hist_i64", ptr(seg_b), ptr(bits_a), H, W, D, nl, C.cast(act4, C.c_void_p), nbins,
+                         C.c_void_p(hist.data_ptr() + 8 * k * nbins), 2 * nbins, C.c_void_p(flag.data_ptr() + 4 * k), 2,
+                         int(HD95_SURFACE_MAX_RADIUS))
             quant = float(np.true_divide(95, np.float32(100)))               # numpy: q / float32(100) for float32 data
-            # dist1[surf2] and dist2[surf1] (:48) for every label: one launch over a device table of volume addresses
-            tab = []
-            for j, lab in enumerate(present):
-                pair = (dist_f[j], dist_m[j])
-                for k in range(2):
-                    tab += [pair[k][0].data_ptr(), pair[k][1].data_ptr(), pair[1 - k][0].data_ptr()]
-            tab_d = torch.tensor(tab, dtype=torch.int64).to(dev)
-            check(L.cvx_surface_hist_batch_i64(ptr(tab_d), 2 * len(present), n, nbins, ptr(hist), ptr(flag), sp))
-            check(L.cvx_hist_percentile_neighbours_batch_i64(ptr(hist), nbins, 2 * len(present), quant, ptr(out3), sp))
-            res = out3.cpu().numpy()
-            if int(flag.cpu().max()) != 0:
+            call(dev, "cvx_hist_percentile_neighbours_batch_i64", ptr(hist), nbins, 2 * nl, quant, ptr(out3))
+            host = tail.cpu().numpy()
+            flags = host[nl * 6:].view(np.int32)[[2 * (lab - 1) + k for lab in present for k in range(2)]]
+            if np.any(flags == 2):               # a surface voxel farther than HD95_SURFACE_MAX_RADIUS rows from its target: the ring
+                # the search would crawl: the transforms take over.  The fixed map's transforms are NOT kept in the caller's cache here
+                # (715 MB per pair at 160x192x224, for a case that should be rare)
+                return cupy_hd95(fixed, moving, num_labels, precision, None, method="edt", counts=cnt)
+            if np.any(flags != 0):
                 raise RuntimeError("cupy_hd95: squared distance exceeds the histogram range")
-        if not present:
-            res = None
+            res = host[:nl * 6].reshape(nl, 2, 3)[[lab - 1 for lab in present]]
+        return _hd95_from_order_stats(res, present, nl, precision, dev)
+    # label range (F.one_hot, :33) and presence in one pass: voxel counts of labels 0 .. num_labels in both maps
+    cnt = label_overlap_counts(fx, mv, nl + 1) if counts is None else counts
+    if cnt.shape != (3, nl + 1):
+        raise ValueError("cupy_hd95: counts must be label_overlap_counts(fixed, moving, num_labels + 1)")
+    if int(cnt[0].sum()) != int(fx.numel()) or int(cnt[1].sum()) != int(fx.numel()):
+        raise RuntimeError("cupy_hd95: class values must be in 0 .. num_labels (F.one_hot, :33)")
+    present = [i for i in range(1, nl + 1) if cnt[0, i] > 0 and cnt[1, i] > 0]
+    if present:
+        if fixed_cache is not None:
+            key = ("edt", prec, nl)
+            if key not in fixed_cache:
+                labs_f = [i for i in range(1, nl + 1) if cnt[0, i] > 0]
+                fixed_cache[key] = (labs_f, transforms(fx, labs_f))
+            labs_f, dist_f_all = fixed_cache[key]
+            dist_f = [dist_f_all[labs_f.index(lab)] for lab in present]
+        else:
+            dist_f_all = transforms(fx, present)
+            dist_f = [dist_f_all[j] for j in range(len(present))]
+        dist_m = transforms(mv, present)
+        hist = torch.empty((2 * len(present), nbins), dtype=torch.int64, device=dev)
+        flag = torch.zeros(2 * len(present), dtype=torch.int32, device=dev)
+        out3 = torch.empty((len(present), 2, 3), dtype=torch.int64, device=dev)
+        quant = float(np.true_divide(95, np.float32(100)))               # numpy: q / float32(100) for float32 data
+        # dist1[surf2] and dist2[surf1] (:48) for every label: one launch over a device table of volume addresses
+        tab = []
+        for j, lab in enumerate(present):
+            pair = (dist_f[j], dist_m[j])
+            for k in range(2):
+                tab += [pair[k][0].data_ptr(), pair[k][1].data_ptr(), pair[1 - k][0].data_ptr()]
+        tab_d = torch.tensor(tab, dtype=torch.int64).to(dev)
+        call(dev, "cvx_surface_hist_batch_i64", ptr(tab_d), 2 * len(present), n, nbins, ptr(hist), ptr(flag))
+        call(dev, "cvx_hist_percentile_neighbours_batch_i64", ptr(hist), nbins, 2 * len(present), quant, ptr(out3))
+        res = out3.cpu().numpy()
+        if int(flag.cpu().max()) != 0:
+            raise RuntimeError("cupy_hd95: squared distance exceeds the histogram range")
+    if not present:
+        res = None
     return _hd95_from_order_stats(res, present, nl, precision, dev)
 
 

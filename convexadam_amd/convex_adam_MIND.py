@@ -18,8 +18,7 @@ from typing import Optional, Union
 import numpy as np
 import torch
 
-from . import _lib
-from ._lib import PairParams, check, f32c, lib, ptr, stream_ptr, workspace
+from ._lib import PairParams, call, f32c, lib, ptr, scratch
 from .convex_adam_utils import MINDSSC, validate_image
 
 _DEFAULT_DEVICE = torch.device("cuda" if torch.cuda.is_available() else "cpu")
@@ -72,12 +71,8 @@ def feature_transform(obj):
     (3,H,W,D) int32 coordinates of the nearest ZERO voxel, scipy's tie-breaking included (csrc/edt.hip)."""
     o = f32c(obj)
     H, W, D = [int(s) for s in o.shape[-3:]]
-    L = lib()
     feat = torch.empty((3, H, W, D), dtype=torch.int32, device=o.device)
-    nws = L.cvx_feature_transform_workspace_bytes(H, W, D)
-    ws = workspace(nws, o.device)
-    with torch.cuda.device(o.device):
-        check(L.cvx_feature_transform_i32(ptr(o), H, W, D, ptr(feat), ptr(ws), nws, stream_ptr(o.device)))
+    call(o.device, "cvx_feature_transform_i32", ptr(o), H, W, D, ptr(feat), *scratch(o.device, "cvx_feature_transform_workspace_bytes", H, W, D))
     return feat
 
 
@@ -91,12 +86,10 @@ def _replicate_fill(img, mask, device):
     if H % 2 or W % 2 or D % 2:
         raise ValueError("masked feature extraction needs even extents (the reference's index expression at "
                          "convex_adam_MIND.py:45 and its x2 up-sampling only line up for even H, W, D)")
-    L = lib()
     im = f32c(img.to(device)).reshape(H, W, D)
     mk = f32c(mask.to(device)).reshape(H, W, D)
     m = torch.empty_like(mk)
-    with torch.cuda.device(device):
-        check(L.cvx_mask_erode_f32(ptr(mk), H, W, D, 0.9, ptr(m), stream_ptr(device)))
+    call(device, "cvx_mask_erode_f32", ptr(mk), H, W, D, 0.9, ptr(m))
     if float(m[::2, ::2, ::2].max()) == 0.0:
         raise ValueError("masked feature extraction: the eroded mask is empty at half resolution (no voxel to replicate from)")
     # edt((m[::2,::2,::2] == 0), return_indices=True): the "objects" are the voxels OUTSIDE the eroded mask
@@ -104,16 +97,13 @@ def _replicate_fill(img, mask, device):
     feat = feature_transform(outside)
     h2, w2, d2 = [int(s) for s in outside.shape]
     lin_d = torch.empty((h2, w2, d2), dtype=torch.int64, device=device)
-    with torch.cuda.device(device):
-        check(L.cvx_feature_flat_index_i64(ptr(feat), h2, w2, d2, W, D, ptr(lin_d), stream_ptr(device)))   # same expression as :45
+    call(device, "cvx_feature_flat_index_i64", ptr(feat), h2, w2, d2, W, D, ptr(lin_d))   # same expression as :45
     half_src = im[::2, ::2, ::2].contiguous()
     half = torch.empty((1, 1) + tuple(half_src.shape), dtype=torch.float32, device=device)
     filled = torch.empty((1, 1, H, W, D), dtype=torch.float32, device=device)
-    with torch.cuda.device(device):
-        check(L.cvx_gather_f32(ptr(half_src), ptr(lin_d), lin_d.numel(), ptr(half), stream_ptr(device)))
+    call(device, "cvx_gather_f32", ptr(half_src), ptr(lin_d), lin_d.numel(), ptr(half))
     up = resize_trilinear(half, (H, W, D))                              # F.interpolate(scale_factor=2, trilinear)
-    with torch.cuda.device(device):
-        check(L.cvx_select_f32(ptr(m), ptr(im), ptr(up), im.numel(), ptr(filled), stream_ptr(device)))
+    call(device, "cvx_select_f32", ptr(m), ptr(im), ptr(up), im.numel(), ptr(filled))
     return filled
 
 
@@ -156,25 +146,17 @@ def _pair_params(adam_mode, cost="ssd", corr_mode="exact", storage="fp32", **fie
                       adam_fast={"exact": 0, "fast": 1, "fast_all": 2}[adam_mode], **fields)
 
 
-def _workspace_bytes(query, *args, otherwise=""):
-    """Result of a workspace-size query of the library; 0 = arguments it refuses -> CvxError with its message."""
-    nws = query(*args)
-    if nws == 0:
-        raise _lib.CvxError(_lib.CVX_ERR_INVALID_ARG, lib().cvx_last_error().decode() or otherwise)
-    return nws
-
-
 def _field_shape(H, W, D, grid_sp, ic, lambda_weight):
     """Full resolution, or the coarse grid for the reference's ic=False & lambda_weight<=0 case."""
     return (3, H, W, D) if ic or lambda_weight > 0 else (3, H // grid_sp, W // grid_sp, D // grid_sp)
 
 
-def _register_device(query, launch, again, n_feat, H, W, D, dev, mind_r, mind_d, lambda_weight, grid_sp, disp_hw, selected_niter, selected_smooth,
+def _register_device(entry, head, again, n_feat, H, W, D, dev, mind_r, mind_d, lambda_weight, grid_sp, disp_hw, selected_niter, selected_smooth,
                      grid_sp_adam, ic, cost_scale, out, profile, cost, n_box, n_spline_pools, corr_mode, storage, adam_mode):
     """What the single-pair device entries share (register_pair_device here, convex_adam_nnUNet.register_labels_device): the reference's
-    behaviour for option values it does not handle, struct cvx_pair_params, workspace and output, the call.  `query`: the entry's
-    workspace query; `launch(p, out, dims, ws, nws)`: its C call, returns the status; `again(selected_smooth, out)`: the same public
-    call with these two arguments replaced.  (The caller has checked that `dev` is a HIP device.)"""
+    behaviour for option values it does not handle, struct cvx_pair_params, workspace and output, the call.  `entry`: the entry point is
+    entry_f32, its workspace query entry_workspace_bytes; `head`: the arguments in front of the parameter struct;
+    `again(selected_smooth, out)`: the same public call with these two arguments replaced.  (The caller has checked that `dev` is a HIP device.)"""
     if lambda_weight > 0 and selected_niter < 1:
         # the reference reads `disp_sample` after a loop that never ran (:181)
         raise UnboundLocalError("local variable 'disp_sample' referenced before assignment "
@@ -194,16 +176,14 @@ def _register_device(query, launch, again, n_feat, H, W, D, dev, mind_r, mind_d,
     p = _pair_params(adam_mode, cost, corr_mode, storage, H=H, W=W, D=D, mind_r=mind_r, mind_d=mind_d, lambda_weight=lambda_weight, grid_sp=grid_sp,
                      disp_hw=disp_hw, selected_niter=selected_niter, selected_smooth=selected_smooth, grid_sp_adam=grid_sp_adam, ic=bool(ic),
                      n_feat=n_feat, cost_scale=cost_scale, n_box=n_box, n_spline_pools=n_spline_pools)
-    nws = _workspace_bytes(query, C.byref(p))
+    ws = scratch(dev, entry + "_workspace_bytes", C.byref(p), required=True)
     oshape = _field_shape(H, W, D, grid_sp, ic, lambda_weight)
     if out is None:
         out = torch.empty(oshape, dtype=torch.float32, device=dev)
-    ws = workspace(nws, dev)
     dims = (C.c_int * 3)()
-    with torch.cuda.device(dev):
-        if profile is not None:
-            lib().cvx_set_profiling(int(profile))
-        check(launch(C.byref(p), ptr(out), C.cast(dims, C.c_void_p), ptr(ws), nws, stream_ptr(dev)))
+    if profile is not None:
+        lib().cvx_set_profiling(int(profile))
+    call(dev, entry + "_f32", *head, C.byref(p), ptr(out), C.cast(dims, C.c_void_p), *ws)
     assert tuple(dims) == tuple(oshape[1:]), (tuple(dims), oshape)
     return out
 
@@ -222,9 +202,8 @@ def register_pair_device(img_fixed=None, img_moving=None, feat_fixed=None, feat_
     a, b, ff, fm, n_feat, H, W, D, dev = _unpack_pair(img_fixed, img_moving, feat_fixed, feat_moving,
                                                       "register_pair_device expects two (H,W,D) volumes of equal shape")
     _require_hip(dev)
-    L = lib()
     return _register_device(
-        L.cvx_register_pair_workspace_bytes, lambda *tail: L.cvx_register_pair_f32(ptr(a), ptr(b), ptr(ff), ptr(fm), *tail),
+        "cvx_register_pair", (ptr(a), ptr(b), ptr(ff), ptr(fm)),
         lambda smooth, out_: register_pair_device(img_fixed, img_moving, feat_fixed, feat_moving, mind_r, mind_d, lambda_weight, grid_sp, disp_hw,
                                                   selected_niter, smooth, grid_sp_adam, ic, cost_scale, out_, profile, cost, n_box, n_spline_pools,
                                                   corr_mode, storage, adam_mode),
@@ -246,16 +225,13 @@ def register_pair_snapshots_device(img_fixed=None, img_moving=None, feat_fixed=N
     p = _pair_params(_resolve_adam_mode(adam_mode, n_spline_pools), H=H, W=W, D=D, mind_r=mind_r, mind_d=mind_d, lambda_weight=lambda_weight,
                      grid_sp=grid_sp, disp_hw=disp_hw, selected_niter=its[-1], grid_sp_adam=grid_sp_adam, ic=bool(ic), n_feat=n_feat,
                      cost_scale=cost_scale, n_spline_pools=n_spline_pools)
-    L = lib()
     it_arr = (C.c_int * len(its))(*its)
     sm_arr = (C.c_int * len(sms))(*sms)
-    nws = _workspace_bytes(L.cvx_register_pair_snapshots_workspace_bytes, C.byref(p), len(its), C.cast(sm_arr, C.c_void_p), len(sms),
-                           otherwise="bad snapshot arguments")
+    ws = scratch(dev, "cvx_register_pair_snapshots_workspace_bytes", C.byref(p), len(its), C.cast(sm_arr, C.c_void_p), len(sms),
+                 required=True, otherwise="bad snapshot arguments")
     out = torch.empty((len(its), len(sms), 3, H, W, D), dtype=torch.float32, device=dev)
-    ws = workspace(nws, dev)
-    with torch.cuda.device(dev):
-        check(L.cvx_register_pair_snapshots_f32(ptr(a), ptr(b), ptr(ff), ptr(fm), C.byref(p), C.cast(it_arr, C.c_void_p), len(its),
-                                                C.cast(sm_arr, C.c_void_p), len(sms), ptr(out), ptr(ws), nws, stream_ptr(dev)))
+    call(dev, "cvx_register_pair_snapshots_f32", ptr(a), ptr(b), ptr(ff), ptr(fm), C.byref(p), C.cast(it_arr, C.c_void_p), len(its),
+         C.cast(sm_arr, C.c_void_p), len(sms), ptr(out), *ws)
     return out
 
 
@@ -275,18 +251,15 @@ def register_pairs_device(imgs_fixed, imgs_moving, outs=None, n_streams=2, mind_
     p = _pair_params(_resolve_adam_mode(adam_mode), H=H, W=W, D=D, mind_r=mind_r, mind_d=mind_d, lambda_weight=lambda_weight, grid_sp=grid_sp,
                      disp_hw=disp_hw, selected_niter=selected_niter, selected_smooth=selected_smooth, grid_sp_adam=grid_sp_adam, ic=bool(ic),
                      cost_scale=cost_scale)
-    L = lib()
-    per = _workspace_bytes(L.cvx_register_pair_workspace_bytes, C.byref(p))
     n_streams = max(1, min(int(n_streams), n, 8))
-    nws = ((per + 4095) // 4096 * 4096) * n_streams
+    ws = scratch(dev, "cvx_register_pair_workspace_bytes", C.byref(p), required=True,
+                 size=lambda per: (per + 4095) // 4096 * 4096 * n_streams)          # one 4 KiB-rounded slot per internal stream
     if outs is None:
         outs = [torch.empty(_field_shape(H, W, D, grid_sp, ic, lambda_weight), dtype=torch.float32, device=dev) for _ in range(n)]
-    ws = workspace(nws, dev)
     arr = lambda ts: (C.c_void_p * n)(*[t.data_ptr() for t in ts])
     dims = (C.c_int * 3)()
-    with torch.cuda.device(dev):
-        check(L.cvx_register_pairs_f32(n, C.cast(arr(fx), C.c_void_p), C.cast(arr(mv), C.c_void_p), None, None, C.byref(p),
-                                       C.cast(arr(outs), C.c_void_p), C.cast(dims, C.c_void_p), ptr(ws), nws, n_streams, stream_ptr(dev)))
+    call(dev, "cvx_register_pairs_f32", n, C.cast(arr(fx), C.c_void_p), C.cast(arr(mv), C.c_void_p), None, None, C.byref(p),
+         C.cast(arr(outs), C.c_void_p), C.cast(dims, C.c_void_p), *ws, n_streams)
     return outs
 
 
@@ -391,12 +364,9 @@ def pack_field_to_host(disp, dtype=torch.float32, sync=True, staging=None):
     _, H, W, D = [int(v) for v in f.shape]
     e, buf = _out_pool.take((H, W, D, 3), torch.float64)
     try:
-        with torch.cuda.device(f.device):
-            if staging is None:
-                check(lib().cvx_pack_field_f64(ptr(f), H, W, D, _QUANT[dtype], C.c_void_p(buf.data_ptr()), stream_ptr(f.device)))
-            else:
-                check(lib().cvx_pack_field_f64(ptr(f), H, W, D, _QUANT[dtype], ptr(staging), stream_ptr(f.device)))
-                buf.copy_(staging, non_blocking=True)
+        call(f.device, "cvx_pack_field_f64", ptr(f), H, W, D, _QUANT[dtype], ptr(buf if staging is None else staging))
+        if staging is not None:
+            buf.copy_(staging, non_blocking=True)
         if sync:
             torch.cuda.current_stream(f.device).synchronize()
         arr = buf.numpy()

@@ -12,7 +12,7 @@ import time
 import numpy as np
 import torch
 
-from ._lib import check, f32c, lib, ptr, require_device_tensor, stream_ptr
+from ._lib import call, f32c, lib, ptr, require_device_tensor
 from .convex_adam_MIND import _register_device, _require_hip, register_pair_device  # noqa: F401  (register_pair_device: the feature entry, re-exported)
 
 
@@ -25,15 +25,13 @@ def _label_channels(pred_fixed, pred_moving, device):
     lm = require_device_tensor(f32c(pred_moving.to(device)), "pred_moving")
     max_label = int(max(float(lf.max()), float(lm.max())))
     hist = torch.zeros((2, max_label + 1), dtype=torch.int64, device=device)
-    L = lib()
-    with torch.cuda.device(device):
-        check(L.cvx_label_histogram_i64(ptr(lf), lf.numel(), max_label, ptr(hist[0]), stream_ptr(device)))
-        check(L.cvx_label_histogram_i64(ptr(lm), lm.numel(), max_label, ptr(hist[1]), stream_ptr(device)))
+    for lab, h in ((lf, hist[0]), (lm, hist[1])):
+        call(device, "cvx_label_histogram_i64", ptr(lab), lab.numel(), max_label, ptr(h))
     h_host = hist.cpu().numpy()
     present = np.zeros(max_label + 1, np.int32)
     weights = np.zeros(max_label + 1, np.float32)
-    Cn = L.cvx_label_weights_host(h_host[0].ctypes.data_as(C.c_void_p), h_host[1].ctypes.data_as(C.c_void_p), max_label,
-                                  present.ctypes.data_as(C.c_void_p), weights.ctypes.data_as(C.c_void_p))
+    Cn = lib().cvx_label_weights_host(h_host[0].ctypes.data_as(C.c_void_p), h_host[1].ctypes.data_as(C.c_void_p), max_label,
+                                      present.ctypes.data_as(C.c_void_p), weights.ctypes.data_as(C.c_void_p))
     present_d = torch.from_numpy(present[:Cn].copy()).to(device)
     weights_d = torch.from_numpy(weights[:Cn].copy()).to(device)
     return lf, lm, present_d, weights_d, Cn
@@ -47,12 +45,10 @@ def extract_features(pred_fixed, pred_moving, mult=10.0, device=None):
     device = lf.device
     H, W, D = [int(s) for s in lf.shape[-3:]]
     V = H * W * D
-    L = lib()
     ff = torch.empty((1, Cn, H, W, D), dtype=torch.float32, device=device)
     fm = torch.empty_like(ff)
-    with torch.cuda.device(device):
-        check(L.cvx_label_features_f32(ptr(lf), V, Cn, ptr(present_d), ptr(weights_d), float(mult), ptr(ff), stream_ptr(device)))
-        check(L.cvx_label_features_f32(ptr(lm), V, Cn, ptr(present_d), ptr(weights_d), float(mult), ptr(fm), stream_ptr(device)))
+    for lab, out in ((lf, ff), (lm, fm)):
+        call(device, "cvx_label_features_f32", ptr(lab), V, Cn, ptr(present_d), ptr(weights_d), float(mult), ptr(out))
     return ff, fm
 
 
@@ -65,15 +61,12 @@ def label_features_pooled(pred_fixed, pred_moving, g1, g2=0, mult=10.0, device=N
     g1, g2 = int(g1), int(g2)
     if g1 < 1 or g2 < 0:
         raise ValueError("label_features_pooled: pooling windows must be g1 >= 1 and g2 >= 0 (0: no second output)")
-    L = lib()
     shape = lambda g: (Cn, H // g, W // g, D // g)
     res = []
     for lab in (lf, lm):
         o1 = torch.empty(shape(g1), dtype=torch.float32, device=device)
         o2 = torch.empty(shape(g2), dtype=torch.float32, device=device) if g2 > 0 else None
-        with torch.cuda.device(device):
-            check(L.cvx_label_features_pooled_f32(ptr(lab), H, W, D, Cn, ptr(present_d), ptr(weights_d), float(mult), g1, ptr(o1), g2, ptr(o2),
-                                                  stream_ptr(device)))
+        call(device, "cvx_label_features_pooled_f32", ptr(lab), H, W, D, Cn, ptr(present_d), ptr(weights_d), float(mult), g1, ptr(o1), g2, ptr(o2))
         res.append((o1, o2))
     return (res[0][0], res[1][0]), ((res[0][1], res[1][1]) if g2 > 0 else None)
 
@@ -89,10 +82,8 @@ def register_labels_device(pred_fixed, pred_moving, mult=10.0, lambda_weight=1.2
     lf, lm, present_d, weights_d, Cn = _label_channels(pred_fixed, pred_moving, pred_fixed.device if pred_fixed.device.type == "cuda" else None)
     H, W, D = [int(s) for s in lf.shape[-3:]]
     _require_hip(lf.device)
-    L = lib()
     return _register_device(
-        L.cvx_register_label_pair_workspace_bytes,
-        lambda *tail: L.cvx_register_label_pair_f32(ptr(lf), ptr(lm), ptr(present_d), ptr(weights_d), float(mult), *tail),
+        "cvx_register_label_pair", (ptr(lf), ptr(lm), ptr(present_d), ptr(weights_d), float(mult)),
         lambda smooth, out_: register_labels_device(lf, lm, mult, lambda_weight, grid_sp, disp_hw, selected_niter, smooth, grid_sp_adam, ic, cost_scale,
                                                     out_, profile, cost, n_box, n_spline_pools, corr_mode, storage, adam_mode),
         Cn, H, W, D, lf.device, 1, 2, lambda_weight, grid_sp, disp_hw, selected_niter, selected_smooth, grid_sp_adam, ic, cost_scale, out, profile,

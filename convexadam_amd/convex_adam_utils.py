@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import CorrOpts, check, f32c, lib, ptr, require_device_tensor, stream_ptr, workspace
+from ._lib import CorrOpts, call, check, f32c, lib, ptr, require_device_tensor, scratch
 
 
 # ---- table helpers (host, exact restatements of torch.linspace / affine_grid) ----------------------
@@ -56,10 +56,8 @@ def MINDSSC(img, radius=2, dilation=2, device='cuda'):
     H, W, D = [int(s) for s in img.shape[2:]]
     x = f32c(img)
     out = torch.empty((1, 12, H, W, D), dtype=torch.float32, device=x.device)
-    nws = lib().cvx_mindssc_workspace_bytes(H, W, D, int(radius), int(dilation))
-    ws = workspace(nws, x.device)
-    with torch.cuda.device(x.device):
-        check(lib().cvx_mindssc_f32(ptr(x), H, W, D, int(radius), int(dilation), ptr(out), ptr(ws), nws, stream_ptr(x.device)))
+    call(x.device, "cvx_mindssc_f32", ptr(x), H, W, D, int(radius), int(dilation), ptr(out),
+         *scratch(x.device, "cvx_mindssc_workspace_bytes", H, W, D, int(radius), int(dilation)))
     return out if img.dtype == torch.float32 else out.to(img.dtype)
 
 
@@ -75,16 +73,14 @@ def mind_pooled(img, radius, dilation, g1, g2=0, device='cuda', return_repairs=F
     g1, g2 = int(g1), int(g2)
     o1 = torch.empty((1, 12, H // g1, W // g1, D // g1), dtype=torch.float32, device=x.device)
     o2 = torch.empty((1, 12, H // g2, W // g2, D // g2), dtype=torch.float32, device=x.device) if g2 > 0 else None
-    nsc = lib().cvx_mindssc_pooled_scratch_bytes(H, W, D, int(radius), int(dilation), g1, g2)
+    nsc = lib().cvx_mindssc_pooled_scratch_bytes(H, W, D, int(radius), int(dilation), g1, g2)     # a second buffer beside the workspace: the call's own
     if x.data_ptr() % 16:                      # (torch allocations are 256-byte aligned; a view may not be)
         x = x.clone()
     sc = torch.empty(max(nsc, 16), dtype=torch.uint8, device=x.device)
-    nws = lib().cvx_mindssc_workspace_bytes(H, W, D, int(radius), int(dilation))
-    ws = workspace(nws, x.device)
     rep = C.c_int(0)
-    with torch.cuda.device(x.device):
-        check(lib().cvx_mindssc_pooled_f32(ptr(x), H, W, D, int(radius), int(dilation), g1, ptr(o1), g2, ptr(o2) if o2 is not None else None,
-                                           ptr(sc) if nsc else None, nsc, ptr(ws), nws, C.byref(rep) if return_repairs else None, stream_ptr(x.device)))
+    call(x.device, "cvx_mindssc_pooled_f32", ptr(x), H, W, D, int(radius), int(dilation), g1, ptr(o1), g2, ptr(o2) if o2 is not None else None,
+         ptr(sc) if nsc else None, nsc, *scratch(x.device, "cvx_mindssc_workspace_bytes", H, W, D, int(radius), int(dilation)),
+         C.byref(rep) if return_repairs else None)
     outs = (o1,) if o2 is None else (o1, o2)
     outs = tuple(o if img.dtype == torch.float32 else o.to(img.dtype) for o in outs)
     if return_repairs:
@@ -98,8 +94,7 @@ def avg_pool(features, g):
     _, Cn, H, W, D = [int(s) for s in features.shape]
     x = f32c(features)
     out = torch.empty((1, Cn, H // g, W // g, D // g), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        check(lib().cvx_avgpool_f32(ptr(x), Cn, H, W, D, int(g), ptr(out), stream_ptr(x.device)))
+    call(x.device, "cvx_avgpool_f32", ptr(x), Cn, H, W, D, int(g), ptr(out))
     return out if features.dtype == torch.float32 else out.to(features.dtype)
 
 
@@ -125,16 +120,13 @@ def correlate(mind_fix, mind_mov, disp_hw, grid_sp, shape, ch=12, cost="ssd", n_
     half = storage == "fp16"
     ssd = torch.empty((n ** 3, h, w, d), dtype=torch.float16 if half else torch.float32, device=f.device)
     am = torch.empty((h, w, d), dtype=torch.int64, device=f.device)
-    nws = lib().cvx_correlate_workspace_bytes(ch, h, w, d, int(disp_hw))
-    ws = workspace(nws, f.device)
+    ws = scratch(f.device, "cvx_correlate_workspace_bytes", ch, h, w, d, int(disp_hw))
     if cost not in ("ssd", "sad") or n_box not in (1, 2) or mode not in ("exact", "fast", "certified"):
         raise ValueError("correlate: cost must be 'ssd' or 'sad', n_box 1 or 2, mode 'exact', 'fast' or 'certified'")
     # mode="certified": the pipeline's internal arithmetic (cvx_corr_opts.fast = 2) -- `ssd` holds the UNSCALED sums (729 x the mean to
     # within 2^-16 relative) and `argmin` is nevertheless the reference's argmin of the EXACT volume (certified, resolved exactly where needed)
     opts = CorrOpts(1 if cost == "sad" else 0, int(n_box), {"exact": 0, "fast": 1, "certified": 2}[mode], 2 if half else 0)
-    with torch.cuda.device(f.device):
-        check(lib().cvx_correlate_ex_f32(ptr(f), ptr(m), ch, h, w, d, int(disp_hw), C.byref(opts), ptr(ssd), ptr(am), ptr(ws), nws,
-                                         stream_ptr(f.device)))
+    call(f.device, "cvx_correlate_ex_f32", ptr(f), ptr(m), ch, h, w, d, int(disp_hw), C.byref(opts), ptr(ssd), ptr(am), *ws)
     if mind_fix.dtype != torch.float32 and not half:
         ssd = ssd.to(mind_fix.dtype)
     return ssd, am
@@ -165,16 +157,12 @@ def coupled_convex(ssd, ssd_argmin, disp_mesh_t, grid_sp, shape, cell_mask=None)
     am = ssd_argmin.to(device=s.device, dtype=torch.int64).contiguous()
     mesh = f32c(disp_mesh_t.to(s.device)).reshape(3, K)
     out = torch.empty((1, 3, h, w, d), dtype=torch.float32, device=s.device)
-    nws = lib().cvx_coupled_convex_workspace_bytes(h, w, d, (n - 1) // 2)
-    ws = workspace(nws, s.device)
-    with torch.cuda.device(s.device):
-        if cell_mask is not None:
-            cm = (cell_mask.to(s.device) != 0).to(torch.uint8).reshape(h, w, d).contiguous()
-            check(lib().cvx_coupled_convex_masked_f32(ptr(s), ptr(am), ptr(mesh), ptr(cm), h, w, d, (n - 1) // 2, ptr(out), ptr(ws), nws,
-                                                      stream_ptr(s.device)))
-        else:
-            fn = lib().cvx_coupled_convex_f16 if half else lib().cvx_coupled_convex_f32
-            check(fn(ptr(s), ptr(am), ptr(mesh), h, w, d, (n - 1) // 2, ptr(out), ptr(ws), nws, stream_ptr(s.device)))
+    ws = scratch(s.device, "cvx_coupled_convex_workspace_bytes", h, w, d, (n - 1) // 2)
+    if cell_mask is not None:
+        cm = (cell_mask.to(s.device) != 0).to(torch.uint8).reshape(h, w, d).contiguous()
+        call(s.device, "cvx_coupled_convex_masked_f32", ptr(s), ptr(am), ptr(mesh), ptr(cm), h, w, d, (n - 1) // 2, ptr(out), *ws)
+    else:
+        call(s.device, "cvx_coupled_convex_f16" if half else "cvx_coupled_convex_f32", ptr(s), ptr(am), ptr(mesh), h, w, d, (n - 1) // 2, ptr(out), *ws)
     return out if disp_mesh_t.dtype == torch.float32 else out.to(disp_mesh_t.dtype)
 
 
@@ -188,11 +176,8 @@ def inverse_consistency(disp_field1s, disp_field2s, iter=20):
     a, b = f32c(d1), f32c(d2)
     o1, o2 = torch.empty_like(a), torch.empty_like(b)
     bh, bw, bd = _base_tables(h, w, d, a.device)
-    nws = lib().cvx_inverse_consistency_workspace_bytes(h, w, d)
-    ws = workspace(nws, a.device)
-    with torch.cuda.device(a.device):
-        check(lib().cvx_inverse_consistency_f32(ptr(a), ptr(b), h, w, d, int(iter), ptr(bh), ptr(bw), ptr(bd), ptr(o1), ptr(o2),
-                                                ptr(ws), nws, stream_ptr(a.device)))
+    call(a.device, "cvx_inverse_consistency_f32", ptr(a), ptr(b), h, w, d, int(iter), ptr(bh), ptr(bw), ptr(bd), ptr(o1), ptr(o2),
+         *scratch(a.device, "cvx_inverse_consistency_workspace_bytes", h, w, d))
     if d1.dtype != torch.float32:
         o1, o2 = o1.to(d1.dtype), o2.to(d1.dtype)
     return o1, o2
@@ -205,8 +190,7 @@ def resize_trilinear(x, size):
     H, W, D = [int(s) for s in size]
     a = f32c(x)
     out = torch.empty((1, Cn, H, W, D), dtype=torch.float32, device=a.device)
-    with torch.cuda.device(a.device):
-        check(lib().cvx_resize_trilinear_f32(ptr(a), Cn, h, w, d, ptr(out), H, W, D, stream_ptr(a.device)))
+    call(a.device, "cvx_resize_trilinear_f32", ptr(a), Cn, h, w, d, ptr(out), H, W, D)
     return out if x.dtype == torch.float32 else out.to(x.dtype)
 
 
@@ -219,8 +203,7 @@ def grid_sample(vol, grid):
         raise ValueError("grid_sample: grid must be (1,ho,wo,do,3)")
     a, g = f32c(vol), f32c(grid.to(vol.device))
     out = torch.empty((1, Cn, ho, wo, do_), dtype=torch.float32, device=a.device)
-    with torch.cuda.device(a.device):
-        check(lib().cvx_grid_sample_f32(ptr(a), Cn, h, w, d, ptr(g), ho, wo, do_, ptr(out), stream_ptr(a.device)))
+    call(a.device, "cvx_grid_sample_f32", ptr(a), Cn, h, w, d, ptr(g), ho, wo, do_, ptr(out))
     return out if vol.dtype == torch.float32 else out.to(vol.dtype)
 
 
@@ -235,15 +218,12 @@ def box_smooth(x, k, passes=1):
         # `selected_smooth` does (convex_adam_MIND.py:184-191)
         for _ in range(int(passes)):
             out = torch.empty((1, Cn, H + 1, W + 1, D + 1), dtype=torch.float32, device=a.device)
-            with torch.cuda.device(a.device):
-                check(lib().cvx_box_grow_f32(ptr(a), Cn, H, W, D, int(k), ptr(out), stream_ptr(a.device)))
+            call(a.device, "cvx_box_grow_f32", ptr(a), Cn, H, W, D, int(k), ptr(out))
             a, H, W, D = out, H + 1, W + 1, D + 1
         return a if x.dtype == torch.float32 else a.to(x.dtype)
     out = torch.empty_like(a)
-    nws = lib().cvx_box_smooth_workspace_bytes(Cn, H, W, D, int(passes))
-    ws = workspace(max(nws, 256), a.device)
-    with torch.cuda.device(a.device):
-        check(lib().cvx_box_smooth_f32(ptr(a), Cn, H, W, D, int(k), int(passes), ptr(out), ptr(ws), nws, stream_ptr(a.device)))
+    call(a.device, "cvx_box_smooth_f32", ptr(a), Cn, H, W, D, int(k), int(passes), ptr(out),
+         *scratch(a.device, "cvx_box_smooth_workspace_bytes", Cn, H, W, D, int(passes)))
     return out if x.dtype == torch.float32 else out.to(x.dtype)
 
 
@@ -255,8 +235,7 @@ def smooth_fast(x, smoother, backward=False):
     if t.numel() != 3 * h * w * d:
         raise ValueError("smooth_fast expects three channels")
     out = torch.empty_like(t)
-    with torch.cuda.device(t.device):
-        check(lib().cvx_smooth_fast_f32(ptr(t), h, w, d, C.byref(smoother.spec), 1 if backward else 0, ptr(out), stream_ptr(t.device)))
+    call(t.device, "cvx_smooth_fast_f32", ptr(t), h, w, d, C.byref(smoother.spec), 1 if backward else 0, ptr(out))
     return out
 
 
@@ -268,8 +247,7 @@ def box3_fast(x):
     if t.numel() != 3 * h * w * d:
         raise ValueError("box3_fast expects three channels")
     out = torch.empty_like(t)
-    with torch.cuda.device(t.device):
-        check(lib().cvx_box3_fast_f32(ptr(t), h, w, d, ptr(out), stream_ptr(t.device)))
+    call(t.device, "cvx_box3_fast_f32", ptr(t), h, w, d, ptr(out))
     return out
 
 
@@ -309,21 +287,14 @@ def adam_run(feat_fix, feat_mov, P0, lambda_weight, niter, cost_scale=12.0, snap
     snaps = sorted(int(i) for i in snapshot_iters)
     snap_arr = (C.c_int * max(len(snaps), 1))(*snaps) if snaps else None
     snap_buf = torch.empty((len(snaps), 3, h, w, d), dtype=torch.float32, device=dev) if snaps else None
-    nws = lib().cvx_adam_workspace_bytes(Cn, h, w, d)
-    ws = workspace(nws, dev)
-    with torch.cuda.device(dev):
-        if mode in ("fast", "fast_all"):
-            check(lib().cvx_adam_run_mode_f32(ptr(F2), ptr(M2), Cn, h, w, d, ptr(P), ptr(m), ptr(v), float(lambda_weight), int(niter),
-                                              int(step0), float(cost_scale), ptr(bh), ptr(bw), ptr(bd), ptr(U), ptr(G),
-                                              C.cast(snap_arr, C.c_void_p) if snaps else None, len(snaps), ptr(snap_buf),
-                                              C.byref(smoother.spec) if smoother is not None else None,
-                                              (1 if mode == "fast" else 2) + (16 if storage == "fp16" else 0), ptr(ws), nws, stream_ptr(dev)))
-        else:
-            check(lib().cvx_adam_run_ex_f32(ptr(F2), ptr(M2), Cn, h, w, d, ptr(P), ptr(m), ptr(v), float(lambda_weight), int(niter),
-                                            int(step0), float(cost_scale), ptr(bh), ptr(bw), ptr(bd), ptr(U), ptr(G),
-                                            C.cast(snap_arr, C.c_void_p) if snaps else None, len(snaps), ptr(snap_buf),
-                                            C.byref(smoother.spec) if smoother is not None else None, 1 if storage == "fp16" else 0,
-                                            ptr(ws), nws, stream_ptr(dev)))
+    # the two entries differ in their name and in what their mode word means
+    if mode in ("fast", "fast_all"):
+        entry, word = "cvx_adam_run_mode_f32", (1 if mode == "fast" else 2) + (16 if storage == "fp16" else 0)
+    else:
+        entry, word = "cvx_adam_run_ex_f32", 1 if storage == "fp16" else 0
+    call(dev, entry, ptr(F2), ptr(M2), Cn, h, w, d, ptr(P), ptr(m), ptr(v), float(lambda_weight), int(niter), int(step0), float(cost_scale),
+         ptr(bh), ptr(bw), ptr(bd), ptr(U), ptr(G), C.cast(snap_arr, C.c_void_p) if snaps else None, len(snaps), ptr(snap_buf),
+         C.byref(smoother.spec) if smoother is not None else None, word, *scratch(dev, "cvx_adam_workspace_bytes", Cn, h, w, d))
     if return_state:
         return U, dict(P=P, m=m, v=v, step=step0 + int(niter), G=G, snapshots=snap_buf)
     return U
@@ -355,8 +326,7 @@ def set_adam_sqrt_table(codes=None, denormal=None, device="cuda"):
     tbl = codes if isinstance(codes, torch.Tensor) else torch.from_numpy(np.array(codes, dtype=np.uint8, order="C"))
     assert tbl.dtype == torch.uint8 and tbl.numel() == 3 << 21, "2-bit codes of 2^24 + 2^23 classes expected"
     _adam_sqrt_table = tbl.to(device).contiguous()                          # (the library keeps its own copy)
-    with torch.cuda.device(_adam_sqrt_table.device):
-        check(lib().cvx_context_set_adam_sqrt_table(None, ptr(_adam_sqrt_table), stream_ptr(_adam_sqrt_table.device)))
+    call(_adam_sqrt_table.device, "cvx_context_set_adam_sqrt_table", None, ptr(_adam_sqrt_table))
     _adam_sqrt_table = None
 
 

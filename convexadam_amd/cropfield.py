@@ -18,7 +18,7 @@ from collections import namedtuple
 import numpy as np
 import torch
 
-from ._lib import _shape, check, f32c, field_operand, lib, ptr, require_device_tensor, stream_ptr
+from ._lib import _shape, call, f32c, field_operand, ptr, require_device_tensor
 
 CROP_FIELD_VOXELS, CROP_OUT_F32, CROP_IDENTITY = 1, 2, 4          # the flags of cvx_crop_field_half_f32
 _FLIP_BITS = {"x": 1, "y": 2, "z": 4}                              # the reference's letters: 'x' = array axis 0, 'y' = 1, 'z' = 2
@@ -142,9 +142,7 @@ def _launch(t, name, planar, grid, geom, full, flip_mask, flags, out_dtype):
     f, grid, cs, vs, _ = field_operand(t.reshape(t.shape[-4:]), grid, planar=planar, f32=True)
     out = torch.empty((3,) + tuple(s // 2 for s in full), dtype=out_dtype, device=f.device)
     g = (C.c_double * 27)(*geom.tolist()) if geom is not None else None
-    with torch.cuda.device(f.device):
-        check(lib().cvx_crop_field_half_f32(ptr(f), cs, vs, grid[0], grid[1], grid[2], g, full[0], full[1], full[2], flip_mask, flags, ptr(out),
-                                            stream_ptr(f.device)))
+    call(f.device, "cvx_crop_field_half_f32", ptr(f), cs, vs, grid[0], grid[1], grid[2], g, full[0], full[1], full[2], flip_mask, flags, ptr(out))
     return out
 
 

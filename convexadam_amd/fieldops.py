@@ -19,8 +19,7 @@ the same bits.  There is no CPU path.
 import numpy as np
 import torch
 
-from . import _field
-from ._lib import check, field_operand_from, ptr, stream_ptr
+from ._lib import call, field_operand_from, ptr
 
 
 def invert_field(disp, max_iters=50, tol=1e-4, return_info=False, device=None):
@@ -40,9 +39,8 @@ def invert_field(disp, max_iters=50, tol=1e-4, return_info=False, device=None):
     residual = torch.empty(shape, dtype=torch.float64, device=dev) if return_info else None
     iters = torch.empty(shape, dtype=torch.uint8, device=dev) if return_info else None
     stats = torch.empty(3, dtype=torch.int64, device=dev) if return_info else None
-    with torch.cuda.device(dev):
-        check(_field.lib().cvx_field_invert_f64(ptr(u), f64, cs, vs, shape[0], shape[1], shape[2], int(max_iters), float(tol), ptr(v), f64,
-                                                cs, vs, ptr(residual), ptr(iters), ptr(stats), stream_ptr(dev)))
+    call(dev, "cvx_field_invert_f64", ptr(u), f64, cs, vs, shape[0], shape[1], shape[2], int(max_iters), float(tol), ptr(v), f64, cs, vs,
+         ptr(residual), ptr(iters), ptr(stats))
     v = v.cpu().numpy() if host else v.to(out_dtype)
     if not return_info:
         return v
@@ -62,9 +60,7 @@ def compose_fields(first, second, device=None):
     if bshape != shape or b.device != a.device:
         raise ValueError("compose_fields: first is %s on %s, second %s on %s" % (shape, a.device, bshape, b.device))
     out = torch.empty_like(a)
-    with torch.cuda.device(a.device):
-        check(_field.lib().cvx_field_compose_f64(ptr(a), a64, acs, avs, ptr(b), b64, bcs, bvs, shape[0], shape[1], shape[2], ptr(out), a64,
-                                                 acs, avs, stream_ptr(a.device)))
+    call(a.device, "cvx_field_compose_f64", ptr(a), a64, acs, avs, ptr(b), b64, bcs, bvs, shape[0], shape[1], shape[2], ptr(out), a64, acs, avs)
     return out.cpu().numpy() if host else out.to(first.dtype)
 
 

@@ -20,7 +20,7 @@ from collections import namedtuple
 import numpy as np
 import torch
 
-from ._lib import check, field_operand, lib, ptr, require_device_tensor, stream_ptr, workspace
+from ._lib import call, field_operand, ptr, require_device_tensor, scratch
 
 Grid = namedtuple("Grid", "size spacing origin direction")          # x, y, z; direction: 9 values, row-major
 Registration = namedtuple("Registration", "field carried_field warped ssim_before ssim_after")
@@ -74,9 +74,7 @@ def resample_device(src, src_grid, out_grid, default=0.0):
     sx, sy, sz = src_grid.size
     ox, oy, oz = out_grid.size
     out = torch.empty((oz, oy, ox), dtype=s.dtype, device=s.device)
-    with torch.cuda.device(s.device):
-        check(lib().cvx_resample_linear_f64(ptr(s), s64, sz, sy, sx, ptr(out), s64, oz, oy, ox, _doubles(M, t), float(default),
-                                            stream_ptr(s.device)))
+    call(s.device, "cvx_resample_linear_f64", ptr(s), s64, sz, sy, sx, ptr(out), s64, oz, oy, ox, _doubles(M, t), float(default))
     if src.dtype in (torch.float32, torch.float64):
         return out
     if src.dtype.is_floating_point:
@@ -121,10 +119,8 @@ def rescale_displacement_field_device(field, moving_grid, fixed_grid, fixed_resa
     warped = torch.empty((mz, my, mx), dtype=warped_dtype, device=dev) if m is not None else None
     M, t = index_map(rg, mg)
     rot, ratio = field_frame(mg, fg, rg)
-    with torch.cuda.device(dev):
-        check(lib().cvx_field_to_grid_f64(ptr(f), f64, cs, vs, shape[0], shape[1], shape[2], _doubles(M, t),
-                                          _doubles(rot), _doubles(ratio), ptr(m), m64, mz, my, mx, ptr(carried), ptr(warped),
-                                          int(warped_dtype == torch.float64), stream_ptr(dev)))
+    call(dev, "cvx_field_to_grid_f64", ptr(f), f64, cs, vs, shape[0], shape[1], shape[2], _doubles(M, t), _doubles(rot), _doubles(ratio),
+         ptr(m), m64, mz, my, mx, ptr(carried), ptr(warped), int(warped_dtype == torch.float64))
     if moving is None:
         return carried
     return (carried, warped) if want_field else warped
@@ -182,15 +178,9 @@ def field_mean_buffer(field, field_grid=None, mask=None, seg=None, seg_grid=None
         sext = tuple(sg.size)[::-1]
         m12 = _doubles(*index_map(sg, grid_of(field_grid)))
     out = torch.empty(4, dtype=torch.float64, device=dev)
-    L = lib()
-    with torch.cuda.device(dev):
-        nbytes = L.cvx_field_mean_workspace_bytes(*shape)
-        if nbytes == 0:
-            check(-1)
-        buf = workspace(nbytes, dev)
-        check(L.cvx_field_mean_f64(ptr(f), f64, cs, vs, shape[0], shape[1], shape[2], _QUANTIZE[quantize], ptr(m), ptr(s),
-                                   kind, sext[0], sext[1], sext[2], m12, C.c_void_p(out.data_ptr()), C.c_void_p(out.data_ptr() + 24), ptr(buf),
-                                   buf.numel(), stream_ptr(dev)))
+    call(dev, "cvx_field_mean_f64", ptr(f), f64, cs, vs, shape[0], shape[1], shape[2], _QUANTIZE[quantize], ptr(m), ptr(s), kind,
+         sext[0], sext[1], sext[2], m12, C.c_void_p(out.data_ptr()), C.c_void_p(out.data_ptr() + 24),
+         *scratch(dev, "cvx_field_mean_workspace_bytes", *shape, required=True))
     return out
 
 

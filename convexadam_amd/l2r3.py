@@ -23,7 +23,7 @@ import time
 import numpy as np
 import torch
 
-from ._lib import check, lib, ptr, require_device_tensor, stream_ptr
+from ._lib import call, check, lib, ptr, require_device_tensor
 
 SNAPSHOT_ITERS, SNAPSHOT_SMOOTHS = (40, 60, 80), (0, 3, 5)
 # the nine result folders of one Adam run, in the reference's order (:22): the smoothing is the slower index
@@ -83,8 +83,7 @@ def ranksum_better(samples, means=None, scale=0.1, sign=1.0, p_threshold=0.05, r
         m = require_device_tensor(means, "means").detach().to(device=dev, dtype=torch.float32).contiguous()
     scores = torch.empty((R, N), dtype=torch.int32, device=dev)
     u2 = torch.empty((R, N, N), dtype=torch.int32, device=dev) if return_u2 else None
-    with torch.cuda.device(dev):
-        check(lib().cvx_ranksum_better_f64(ptr(x), ptr(m), float(scale), float(sign), R, N, S, crit, ptr(scores), ptr(u2), stream_ptr(dev)))
+    call(dev, "cvx_ranksum_better_f64", ptr(x), ptr(m), float(scale), float(sign), R, N, S, crit, ptr(scores), ptr(u2))
     return (scores, u2) if return_u2 else scores
 
 

@@ -15,8 +15,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._lib import check, f32c, ptr, require_device_tensor, stream_ptr, workspace
-from ._prep import CVX_PREP_CLAMP, CVX_PREP_POSITIVE, lib
+from ._lib import CVX_PREP_CLAMP, CVX_PREP_POSITIVE, call, f32c, ptr, require_device_tensor, scratch
 
 
 def _volume(img, name):
@@ -32,15 +31,9 @@ def _stats(x, flags=0, clamp=(0.0, 0.0), quantiles=None, moments=False):
     n = x.numel()
     params = torch.empty(4, dtype=torch.float32, device=x.device)
     mom = torch.empty(3, dtype=torch.float64, device=x.device) if moments else None
-    L = lib()
-    with torch.cuda.device(x.device):
-        nws = L.cvx_prep_stats_workspace_bytes(n)
-        if not nws:
-            check(-1)
-        ws = workspace(nws, x.device)
-        q = quantiles or (0.0, 0.0)
-        check(L.cvx_prep_stats_f32(ptr(x), n, flags, float(clamp[0]), float(clamp[1]), 2 if quantiles else 0, float(q[0]), float(q[1]),
-                                   ptr(params), ptr(mom), ptr(ws), nws, stream_ptr(x.device)))
+    q = quantiles or (0.0, 0.0)
+    call(x.device, "cvx_prep_stats_f32", ptr(x), n, flags, float(clamp[0]), float(clamp[1]), 2 if quantiles else 0, float(q[0]), float(q[1]),
+         ptr(params), ptr(mom), *scratch(x.device, "cvx_prep_stats_workspace_bytes", n, required=True))
     return (params, mom) if moments else params
 
 
@@ -49,8 +42,7 @@ def _normalise(x, mode, params=None, host=None, out=None):
     if out is None:
         out = torch.empty_like(x)
     hp = (C.c_float * 4)(*host) if host is not None else None
-    with torch.cuda.device(x.device):
-        check(lib().cvx_prep_normalise_f32(ptr(x), x.numel(), ptr(params), hp, mode, ptr(out), stream_ptr(x.device)))
+    call(x.device, "cvx_prep_normalise_f32", ptr(x), x.numel(), ptr(params), hp, mode, ptr(out))
     return out
 
 
@@ -102,14 +94,8 @@ def _nonzero_mask(data):
     mask = torch.empty(shape, dtype=torch.uint8, device=x.device)
     box = torch.empty(6, dtype=torch.int32, device=x.device)
     rounds = C.c_int(0)
-    L = lib()
-    with torch.cuda.device(x.device):
-        nws = L.cvx_prep_nonzero_mask_workspace_bytes(H, W, D)
-        if not nws:
-            check(-1)
-        ws = workspace(nws, x.device)
-        check(L.cvx_prep_nonzero_mask_u8(ptr(x), int(x.shape[0]), H, W, D, ndim, ptr(mask), ptr(box), None, C.byref(rounds), ptr(ws), nws,
-                                         stream_ptr(x.device)))
+    call(x.device, "cvx_prep_nonzero_mask_u8", ptr(x), int(x.shape[0]), H, W, D, ndim, ptr(mask), ptr(box), None, C.byref(rounds),
+         *scratch(x.device, "cvx_prep_nonzero_mask_workspace_bytes", H, W, D, required=True))
     return mask.view(torch.bool), box, int(rounds.value)
 
 
@@ -145,8 +131,7 @@ def get_bbox_from_mask(mask, outside_value=0):
         m = (mask != outside_value).to(torch.uint8).contiguous()
     box = torch.empty(6, dtype=torch.int32, device=m.device)
     H, W, D = [int(s) for s in m.shape]
-    with torch.cuda.device(m.device):
-        check(lib().cvx_prep_mask_bbox_i32(ptr(m), H, W, D, ptr(box), None, stream_ptr(m.device)))
+    call(m.device, "cvx_prep_mask_bbox_i32", ptr(m), H, W, D, ptr(box), None)
     return _box_list(box)
 
 

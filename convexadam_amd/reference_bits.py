@@ -25,7 +25,7 @@ differs by as much from itself across hosts).  Cost when installed: a dependent 
 import numpy as np
 import torch
 
-from ._lib import check, lib, ptr, stream_ptr
+from ._lib import call, check, lib, ptr
 from .convex_adam_utils import set_adam_sqrt_table
 
 
@@ -43,8 +43,7 @@ def device_expf(x):
     """The library's expf on a float32 device tensor (cvx_expf_f32)."""
     x = x.contiguous()
     out = torch.empty_like(x)
-    with torch.cuda.device(x.device):
-        check(lib().cvx_expf_f32(ptr(x), ptr(out), x.numel(), stream_ptr(x.device)))
+    call(x.device, "cvx_expf_f32", ptr(x), ptr(out), x.numel())
     return out
 
 
@@ -100,8 +99,7 @@ def set_mind_exp_table(table=None, first=EXP_FIRST, count=EXP_COUNT, device="cud
     t = table if isinstance(table, torch.Tensor) else torch.from_numpy(np.array(table, dtype=np.uint8, order="C"))
     t = t.to(device).contiguous()
     assert t.dtype == torch.uint8 and t.numel() * 4 >= count
-    with torch.cuda.device(t.device):                                                # (the library keeps its own copy)
-        check(lib().cvx_context_set_mind_exp_table(None, ptr(t), int(first), int(count), stream_ptr(t.device)))
+    call(t.device, "cvx_context_set_mind_exp_table", None, ptr(t), int(first), int(count))          # (the library keeps its own copy)
 
 
 def set_mean_threads(threads=0):

@@ -8,7 +8,7 @@ import ctypes as C
 
 import torch
 
-from ._lib import CVX_ERR_INVALID_ARG, _shape, check, f32c, lib, ptr, require_device_tensor, stream_ptr, workspace
+from ._lib import _shape, call, f32c, ptr, require_device_tensor, scratch
 
 _MODES = {"bilinear": 0, "nearest": 1}
 
@@ -27,8 +27,8 @@ def _point_pair(a, b, names, min_n, exact_cols=None):
     return n[0]
 
 
-def _fit(library, entry, fixed, moving, want_inliers, *model_args):
-    """One launch of library().<entry>_f32 (cvx_rigid_lts, cvx_affine_lts) -> X (4, 4) float32[, the (N,) bool inlier mask]; model_args:
+def _fit(entry, fixed, moving, want_inliers, *model_args):
+    """One launch of <entry>_f32 (cvx_rigid_lts, cvx_affine_lts) -> X (4, 4) float32[, the (N,) bool inlier mask]; model_args:
     what the entry point takes between n and X (iters; the affine one also `normal`)"""
     f = f32c(require_device_tensor(fixed, "fixed"))
     m = f32c(require_device_tensor(moving, "moving"))
@@ -37,12 +37,8 @@ def _fit(library, entry, fixed, moving, want_inliers, *model_args):
     n = int(f.shape[0])
     X = torch.empty((4, 4), dtype=torch.float32, device=f.device)
     mask = torch.empty(n, dtype=torch.uint8, device=f.device) if want_inliers else None
-    L = library()
-    with torch.cuda.device(f.device):
-        nws = getattr(L, entry + "_workspace_bytes")(n)
-        ws = workspace(nws, f.device)
-        check(getattr(L, entry + "_f32")(ptr(f), int(f.shape[1]), ptr(m), int(m.shape[1]), n, *model_args, ptr(X), ptr(mask), ptr(ws), nws,
-                                         stream_ptr(f.device)))
+    call(f.device, entry + "_f32", ptr(f), int(f.shape[1]), ptr(m), int(m.shape[1]), n, *model_args, ptr(X), ptr(mask),
+         *scratch(f.device, entry + "_workspace_bytes", n))
     return (X, mask.bool()) if want_inliers else X
 
 
@@ -56,7 +52,7 @@ def find_rigid_3d(x, y):
     """(4, 4) T = [R t; 0 0 0 1] with y[:, :3] ~ x[:, :3] R^T + t, R the optimal proper rotation (convex_adam_utils.py:173-184).
     x, y: (N, k >= 3) device tensors, N >= 2.  Raises CvxError on a non-finite coordinate (the reference's torch.svd raises too)."""
     _point_pair(x, y, ("x", "y"), 2)
-    return _fit(lib, "cvx_rigid_lts", x, y, False, 1)
+    return _fit("cvx_rigid_lts", x, y, False, 1)
 
 
 def least_trimmed_rigid(fixed_pts, moving_pts, iter=5, return_inliers=False):
@@ -65,7 +61,7 @@ def least_trimmed_rigid(fixed_pts, moving_pts, iter=5, return_inliers=False):
     (N, 4) device tensors (homogeneous points).  Returns T (4, 4) float32, and with return_inliers=True also the (N,) bool mask of the
     points the returned fit used."""
     _point_pair(fixed_pts, moving_pts, ("fixed_pts", "moving_pts"), 2, 4)
-    return _fit(lib, "cvx_rigid_lts", fixed_pts, moving_pts, bool(return_inliers), _trimmed_iters(iter))
+    return _fit("cvx_rigid_lts", fixed_pts, moving_pts, bool(return_inliers), _trimmed_iters(iter))
 
 
 def affine_warp(vol, theta, size=None, mode="bilinear"):
@@ -95,8 +91,7 @@ def affine_warp(vol, theta, size=None, mode="bilinear"):
     if th.device != a.device:
         raise ValueError("theta must live on vol's device (%s, %s)" % (th.device, a.device))
     out = torch.empty((Cn, ho, wo, do_), dtype=torch.float32, device=a.device)
-    with torch.cuda.device(a.device):
-        check(lib().cvx_affine_warp_f32(ptr(a), Cn, h, w, d, ptr(th), ho, wo, do_, _MODES[mode], ptr(out), stream_ptr(a.device)))
+    call(a.device, "cvx_affine_warp_f32", ptr(a), Cn, h, w, d, ptr(th), ho, wo, do_, _MODES[mode], ptr(out))
     return out.unsqueeze(0) if len(vs) == 5 else out
 
 
@@ -121,8 +116,7 @@ def threshold_pool_mask(img, thresh, grid_sp):
         raise ValueError("grid_sp = %r must lie in 1..64 and fit the extent %s" % (grid_sp, (H, W, D)))
     a = f32c(require_device_tensor(img, "img"))
     out = torch.empty((H // g, W // g, D // g), dtype=torch.uint8, device=a.device)
-    with torch.cuda.device(a.device):
-        check(lib().cvx_threshold_pool_mask_u8(ptr(a), H, W, D, t, g, ptr(out), stream_ptr(a.device)))
+    call(a.device, "cvx_threshold_pool_mask_u8", ptr(a), H, W, D, t, g, ptr(out))
     return out.view(torch.bool)
 
 
@@ -145,8 +139,7 @@ def label_centroids(seg, max_label, return_counts=False):
     m = _max_label(max_label)
     a = f32c(require_device_tensor(seg, "seg"))
     acc = torch.empty((m + 1, 4), dtype=torch.int64, device=a.device)
-    with torch.cuda.device(a.device):
-        check(lib().cvx_label_centroids_i64(ptr(a), H, W, D, m, ptr(acc), stream_ptr(a.device)))
+    call(a.device, "cvx_label_centroids_i64", ptr(a), H, W, D, m, ptr(acc))
     acc = acc.cpu()
     counts = acc[:, 0]
     cent = acc[:, 1:].to(torch.float64) / counts.to(torch.float64).unsqueeze(1)        # 0 / 0 = NaN for an absent label
@@ -219,12 +212,8 @@ def convex_stage(feat_fix, feat_mov, grid_sp, disp_hw, shape, mask_fix=None, mas
     p = StageParams(sf[0], hwd[0], hwd[1], hwd[2], hw, g, it, H, W, D)
     coarse = torch.empty((1, 3) + hwd, dtype=torch.float32, device=dev)
     hr = torch.empty((1, 3, H, W, D), dtype=torch.float32, device=dev) if full_res else None
-    with torch.cuda.device(dev):
-        nws = lib().cvx_convex_stage_workspace_bytes(C.byref(p))
-        if nws == 0:
-            check(CVX_ERR_INVALID_ARG)
-        ws = workspace(nws, dev)
-        check(lib().cvx_convex_stage_f32(ptr(f), ptr(m), ptr(mf), ptr(mm), C.byref(p), ptr(coarse), ptr(hr), ptr(ws), nws, stream_ptr(dev)))
+    call(dev, "cvx_convex_stage_f32", ptr(f), ptr(m), ptr(mf), ptr(mm), C.byref(p), ptr(coarse), ptr(hr),
+         *scratch(dev, "cvx_convex_stage_workspace_bytes", C.byref(p), required=True))
     return coarse, hr
 
 
@@ -257,11 +246,8 @@ def rigid_samples(coarse_field, mask_coarse, grid_sp, shape):
     T1 = torch.empty((v, 4), dtype=torch.float32, device=dev)
     T2 = torch.empty((v, 4), dtype=torch.float32, device=dev)
     count = C.c_int64(0)
-    with torch.cuda.device(dev):
-        nws = lib().cvx_rigid_samples_workspace_bytes(hwd[0], hwd[1], hwd[2], H, W, D)
-        ws = workspace(nws, dev)
-        check(lib().cvx_rigid_samples_f32(ptr(c), ptr(m), hwd[0], hwd[1], hwd[2], H, W, D, ptr(T1), ptr(T2), C.byref(count), ptr(ws), nws,
-                                          stream_ptr(dev)))
+    call(dev, "cvx_rigid_samples_f32", ptr(c), ptr(m), hwd[0], hwd[1], hwd[2], H, W, D, ptr(T1), ptr(T2), C.byref(count),
+         *scratch(dev, "cvx_rigid_samples_workspace_bytes", hwd[0], hwd[1], hwd[2], H, W, D))
     M = int(count.value)
     if M < 2:
         raise ValueError("mask_coarse selects %d cells; the fit needs at least 2" % M)
@@ -395,24 +381,23 @@ def _field_samples(disp_hr, mask_coarse, grid_sp):
         raise ValueError("mask_coarse must be (%d, %d, %d) (optionally with leading 1s), got %s" % (Hc, Wc, Dc, ms))
     disp = f32c(require_device_tensor(disp_hr, "disp_hr")).reshape(3, H, W, D)
     dev = disp.device
-    with torch.cuda.device(dev):
-        bh, bw, bd = _base_tables(H, W, D, dev)
-        ident = torch.stack([bd.view(1, 1, D).expand(H, W, D), bw.view(1, W, 1).expand(H, W, D), bh.view(H, 1, 1).expand(H, W, D)])
-        # disp_hr / (size - 1) * 2 flipped to (x, y, z), divided by a DEVICE tensor as the reference does (true division; a Python
-        # scalar divisor would be applied as a multiplication by its reciprocal on the device)
-        scale = torch.tensor([D - 1, W - 1, H - 1], dtype=torch.float32, device=dev).view(3, 1, 1, 1)
-        moved = ident + disp.flip(0) / scale * 2
-        idx = torch.nonzero(torch.as_tensor(mask_coarse).to(dev).reshape(-1)).reshape(-1)
-        M = int(idx.numel())
-        if M < 2:
-            raise ValueError("mask_coarse selects %d cells; the fit needs at least 2" % M)
-        ch, cw, cd = _base_tables(Hc, Wc, Dc, dev)
-        pts = torch.stack([cd[idx % Dc], cw[(idx // Dc) % Wc], ch[idx // (Wc * Dc)]], 1).contiguous()
-        out = []
-        for v in (ident, moved):
-            s = torch.empty((3, M), dtype=torch.float32, device=dev)
-            check(lib().cvx_grid_sample_f32(ptr(v), 3, H, W, D, ptr(pts), M, 1, 1, ptr(s), stream_ptr(dev)))
-            out.append(torch.cat([s.t(), torch.ones((M, 1), dtype=torch.float32, device=dev)], 1).contiguous())
+    bh, bw, bd = _base_tables(H, W, D, dev)
+    ident = torch.stack([bd.view(1, 1, D).expand(H, W, D), bw.view(1, W, 1).expand(H, W, D), bh.view(H, 1, 1).expand(H, W, D)])
+    # disp_hr / (size - 1) * 2 flipped to (x, y, z), divided by a DEVICE tensor as the reference does (true division; a Python
+    # scalar divisor would be applied as a multiplication by its reciprocal on the device)
+    scale = torch.tensor([D - 1, W - 1, H - 1], dtype=torch.float32, device=dev).view(3, 1, 1, 1)
+    moved = ident + disp.flip(0) / scale * 2
+    idx = torch.nonzero(torch.as_tensor(mask_coarse).to(dev).reshape(-1)).reshape(-1)
+    M = int(idx.numel())
+    if M < 2:
+        raise ValueError("mask_coarse selects %d cells; the fit needs at least 2" % M)
+    ch, cw, cd = _base_tables(Hc, Wc, Dc, dev)
+    pts = torch.stack([cd[idx % Dc], cw[(idx // Dc) % Wc], ch[idx // (Wc * Dc)]], 1).contiguous()
+    out = []
+    for v in (ident, moved):
+        s = torch.empty((3, M), dtype=torch.float32, device=dev)
+        call(dev, "cvx_grid_sample_f32", ptr(v), 3, H, W, D, ptr(pts), M, 1, 1, ptr(s))
+        out.append(torch.cat([s.t(), torch.ones((M, 1), dtype=torch.float32, device=dev)], 1).contiguous())
     return out[0], out[1]
 
 

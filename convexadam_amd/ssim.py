@@ -12,11 +12,9 @@ is zeros and the border is not renormalised, exactly as F.conv3d(padding=window_
 even window makes the reference's output one voxel larger per axis, a larger one adds taps below 1e-6; both raise, nothing is routed to
 another implementation.  Nothing here synchronises with the host.
 """
-import ctypes as C
-
 import torch
 
-from ._lib import check, f32c, lib, ptr, require_device_tensor, stream_ptr, workspace
+from ._lib import call, f32c, ptr, require_device_tensor, scratch
 
 # (shortest H chunk, W tile, D tile) of csrc/ssim.hip: SSIM_MIN_HCHUNK, SSIM_TW, SSIM_TD.  A workgroup owns a W x D tile and walks a chunk
 # of H; results do not depend on any of the three (tests/test_gpu_ssim.py walks the extents around them)
@@ -57,12 +55,9 @@ def _run(img1, img2, window_size, want_map=False, want_mean=False, want_slices=F
     out_map = torch.empty_like(a) if want_map else None
     mean = torch.empty((), dtype=torch.float32, device=dev) if want_mean else None
     slices = torch.empty((n, d), dtype=torch.float32, device=dev) if want_slices else None
-    L = lib()
-    with torch.cuda.device(dev):
-        nbytes = L.cvx_ssim3d_workspace_bytes(n, c, h, w, d, ws) if (want_mean or want_slices) else 0
-        buf = workspace(nbytes, dev) if nbytes else None            # (a refused window: the call below says why)
-        check(L.cvx_ssim3d_f32(ptr(a), ptr(b), n, c, h, w, d, ws, ptr(out_map), ptr(mean), ptr(slices), ptr(buf),
-                               C.c_size_t(buf.numel() if buf is not None else 0), stream_ptr(dev)))
+    # (only the means need scratch; a refused window answers 0 and the call says why)
+    buf = scratch(dev, "cvx_ssim3d_workspace_bytes", n, c, h, w, d, ws) if (want_mean or want_slices) else (None, 0)
+    call(dev, "cvx_ssim3d_f32", ptr(a), ptr(b), n, c, h, w, d, ws, ptr(out_map), ptr(mean), ptr(slices), *buf)
     return out_map, mean, slices
 
 
@@ -99,8 +94,7 @@ def warp_device(moving, disp):
     m = moving.detach().to(torch.float64).contiguous()
     f = field.detach().to(dev, torch.float64).contiguous()
     out = torch.empty_like(m)
-    with torch.cuda.device(dev):
-        check(lib().cvx_map_coordinates_linear_f64(ptr(m), ptr(f), shape[0], shape[1], shape[2], ptr(out), stream_ptr(dev)))
+    call(dev, "cvx_map_coordinates_linear_f64", ptr(m), ptr(f), shape[0], shape[1], shape[2], ptr(out))
     return out.to(torch.float32)
 
 

@@ -6,7 +6,7 @@ script runs on the registered field after its Adam stage.
 """
 import torch
 
-from ._lib import _shape, check, f32c, lib, ptr, require_device_tensor, stream_ptr, workspace
+from ._lib import _shape, call, f32c, ptr, require_device_tensor, scratch
 
 _MAX_RHS = 4
 
@@ -43,16 +43,14 @@ class TPS:
             raise ValueError("f must be (n, f_dim) with n = %d and f_dim >= 1, got %s" % (n, fs))
         c = f32c(require_device_tensor(c, "c"))
         parts = []
-        with torch.cuda.device(c.device):
-            for fk in _columns(f, "f"):
-                nr = int(fk.shape[1])
-                theta = torch.zeros((n + 4, nr), dtype=torch.float32, device=c.device)
-                nws = lib().cvx_tps_fit_workspace_bytes(n, nr)
-                if nws == 0:
-                    raise ValueError("TPS.fit: n = %d centres is outside what the library supports" % n)
-                ws = workspace(nws, c.device)
-                check(lib().cvx_tps_fit_f32(ptr(c), ptr(fk), n, nr, float(lambd), ptr(theta), ptr(ws), nws, stream_ptr(c.device)))
-                parts.append(theta)
+        for fk in _columns(f, "f"):
+            nr = int(fk.shape[1])
+            theta = torch.zeros((n + 4, nr), dtype=torch.float32, device=c.device)
+            ws = scratch(c.device, "cvx_tps_fit_workspace_bytes", n, nr)
+            if ws[1] == 0:
+                raise ValueError("TPS.fit: n = %d centres is outside what the library supports" % n)
+            call(c.device, "cvx_tps_fit_f32", ptr(c), ptr(fk), n, nr, float(lambd), ptr(theta), *ws)
+            parts.append(theta)
         return parts[0] if len(parts) == 1 else torch.cat(parts, 1)
 
     @staticmethod
@@ -78,12 +76,11 @@ class TPS:
         x = f32c(require_device_tensor(x, "x"))
         c = f32c(require_device_tensor(c, "c"))
         parts = []
-        with torch.cuda.device(x.device):
-            for th in _columns(theta, "theta"):
-                nr = int(th.shape[1])
-                out = torch.empty((m, nr), dtype=torch.float32, device=x.device)
-                check(lib().cvx_tps_eval_f32(ptr(x), m, ptr(c), ptr(th), n, nr, ptr(out), stream_ptr(x.device)))
-                parts.append(out)
+        for th in _columns(theta, "theta"):
+            nr = int(th.shape[1])
+            out = torch.empty((m, nr), dtype=torch.float32, device=x.device)
+            call(x.device, "cvx_tps_eval_f32", ptr(x), m, ptr(c), ptr(th), n, nr, ptr(out))
+            parts.append(out)
         return parts[0] if len(parts) == 1 else torch.cat(parts, 1)
 
 
@@ -99,12 +96,11 @@ def tps_dense(c, theta, size):
         raise ValueError("size must be three positive ints, got %r" % (size,))
     c = f32c(require_device_tensor(c, "c"))
     parts = []
-    with torch.cuda.device(c.device):
-        for th in _columns(theta, "theta"):
-            nr = int(th.shape[1])
-            out = torch.empty((nr, s0, s1, s2), dtype=torch.float32, device=c.device)
-            check(lib().cvx_tps_dense_f32(s0, s1, s2, ptr(c), ptr(th), n, nr, ptr(out), stream_ptr(c.device)))
-            parts.append(out)
+    for th in _columns(theta, "theta"):
+        nr = int(th.shape[1])
+        out = torch.empty((nr, s0, s1, s2), dtype=torch.float32, device=c.device)
+        call(c.device, "cvx_tps_dense_f32", s0, s1, s2, ptr(c), ptr(th), n, nr, ptr(out))
+        parts.append(out)
     return parts[0] if len(parts) == 1 else torch.cat(parts, 0)
 
 
@@ -118,8 +114,7 @@ def resize_trilinear_ac(x, size):
     H, W, D = [int(s) for s in size]
     a = f32c(require_device_tensor(x, "x"))
     out = torch.empty((Nb, Cn, H, W, D), dtype=torch.float32, device=a.device)
-    with torch.cuda.device(a.device):
-        check(lib().cvx_resize_trilinear_ac_f32(ptr(a), Nb * Cn, h, w, d, ptr(out), H, W, D, stream_ptr(a.device)))
+    call(a.device, "cvx_resize_trilinear_ac_f32", ptr(a), Nb * Cn, h, w, d, ptr(out), H, W, D)
     return out
 
 
