@@ -1,7 +1,8 @@
 """ctypes binding of libconvexadam_hip.so and the one call path into it.
 
 One table per public header: SIGNATURES (include/convexadam_hip.h), PREP_SIGNATURES (convexadam_prep.h), FIELD_SIGNATURES
-(convexadam_field.h), AFFINE_SIGNATURES (convexadam_affine.h); lib() types all four when it loads the library.  Every entry point that
+(convexadam_field.h), AFFINE_SIGNATURES (convexadam_affine.h); lib() types all four when it loads the library.  SOFT_SIGNATURES
+(convexadam_soft.h) is typed by soft_lib(), on the first call of convexadam_amd.confidence, as strictly and by name.  Every entry point that
 takes a stream is entered through call(), every scratch buffer comes from scratch().
 
 The HIP library IS the product: there is no CPU or PyTorch fallback.  If the shared object is
@@ -205,8 +206,15 @@ AFFINE_SIGNATURES = {
     "cvx_affine_field_f64": (_i, [_vp, _i, _i, _i] + _FIELD + _FIELD + [_vp]),
 }
 
+# include/convexadam_soft.h (typed by soft_lib() below, not at load)
+SOFT_SIGNATURES = {
+    "cvx_soft_stats_workspace_bytes": (_sz, [_i] * 4),
+    "cvx_soft_stats_f32": (_i, [_vp, _i, _vp, _f, _f, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+}
+
 _REBUILD = "rebuild with `python -m convexadam_amd.csrc.build`"
 _lib = None
+_soft_typed = None          # the handle soft_lib() has typed SOFT_SIGNATURES on
 _lock = threading.Lock()
 
 
@@ -244,6 +252,16 @@ def lib():
                                        "(there is no CPU fallback)" % LIB_PATH)
                 _lib = _typed(C.CDLL(LIB_PATH))
     return _lib
+
+
+def soft_lib():
+    """lib() with the entry points of include/convexadam_soft.h typed as well: a library that lacks one is refused by name, as at load.
+    (Not part of _typed(): tests/test_call_path.py loads stand-in handles that hold the four tables above and nothing else.)"""
+    global _soft_typed
+    L = lib()
+    if _soft_typed is not L:
+        _soft_typed = bind(L, SOFT_SIGNATURES)
+    return L
 
 
 def _last_error():

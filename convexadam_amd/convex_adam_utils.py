@@ -475,3 +475,6 @@ from .fieldops import apply_convex_inverse, compose_fields, invert_field  # noqa
 # the affine model: least-trimmed affine fit, the affine as a field, affine pre-alignment (l2r_2020_convexAdam_CuRIOUS.py:272-278): csrc/affine.hip
 from .affine import (affine_from_field, affine_to_field, convex_adam_affine, find_affine_3d, least_trimmed_affine,  # noqa: E402,F401
                      least_trimmed_squares, register_with_affine)
+# the soft reading of the cost volume -- mean, covariance, entropy per coarse cell (no counterpart in the reference): csrc/softstats.hip
+from .confidence import (Confidence, convex_confidence, soft_covariance, soft_displacement, soft_entropy, soft_sigma,  # noqa: E402,F401
+                         soft_stats)
