@@ -84,10 +84,15 @@ __global__ __launch_bounds__(256) void k_mind_stats_init(const float* part, int 
 // clamp bounds of the normalisation from the exact partial sums (every consumer evaluates them itself: a handful of scalar
 // operations instead of a one-thread launch between the two passes)
 __device__ __forceinline__ void mind_bounds(const MindStats* __restrict__ st, double count, float& lo, float& hi) {
-    const float gm = st->use_override ? st->mean_override : (float)((st->a1 + (st->a2 + st->a3)) / count);
+    float gm = st->use_override ? st->mean_override : (float)((st->a1 + (st->a2 + st->a3)) / count);
+    // an infinite voxel: the reference's shifts are convolutions with one-hot kernels (:52-53), 0 * Inf = NaN reaches its mean; here the
+    // voxel gives infinite variances, whose sum in torch's order (mean_override) is Inf.  (imin / imax skip NaN voxels: those poison the sums)
+    if (__builtin_isinf(st->imin) || __builtin_isinf(st->imax)) gm = __builtin_nanf("");
     lo = (float)((double)gm * 0.001);      // python: mind_var.mean().item()*0.001   (:61)
     hi = (float)((double)gm * 1000.0);
 }
+// a NaN mean: some variance is NaN (a NaN voxel; an infinite one: inf - inf in the split sums) -- the reference's clamp then returns NaN everywhere
+__device__ __forceinline__ bool mind_nan_bounds(float lo, float hi) { return lo != lo || hi != hi; }
 
 // ---- the tiled stencil ---------------------------------------------------------------------------
 // TX = tile width (64, or 32 when radius + dilation is too large for the 160 KB of LDS), NT = TX / RUN * TY * TZ threads
@@ -260,6 +265,8 @@ __device__ __forceinline__ void mind_normalise(float (&r)[12], float lo, float h
     float var = fdiv(sum, 12.0f);
     var = var < lo ? lo : var;
     var = var > hi ? hi : var;
+    // torch.clamp propagates a NaN BOUND too (a NaN or infinite voxel makes the global mean NaN): every variance, hence every value, is NaN
+    if (mind_nan_bounds(lo, hi)) var = lo + hi;      // the bounds come from the statistics block: wave-uniform
     if (!et.tbl) {                                   // kernel argument: wave-uniform
 #pragma unroll
         for (int c = 0; c < 12; ++c) r[c] = cvx_expf(-fdiv(r[c], var));
@@ -628,8 +635,8 @@ __global__ __launch_bounds__(MR_NT) void k_mind_repair(const float* __restrict__
         if (mine < nblk) {
             const unsigned bmin = blk[mine], bmax = blk[nblk + mine], bz = blk[2 * (size_t)nblk + mine];
             const float fmin = __uint_as_float(bmin), fmax = __uint_as_float(bmax);
-            // (NaN variances: bits above infinity -- recomputed, whatever the bounds are)
-            bad = force != 0 || fmin < lo || fmax > hi || bmax > 0x7f800000u || (bz != 0u && !(lo > 0.0f));
+            // (NaN variances: bits above infinity -- recomputed, whatever the bounds are; NaN bounds: every block, all-zero voxels included)
+            bad = force != 0 || mind_nan_bounds(lo, hi) || fmin < lo || fmax > hi || bmax > 0x7f800000u || (bz != 0u && !(lo > 0.0f));
         }
         unsigned long long todo = __ballot(bad);              // the same in every wavefront of the workgroup
         while (todo) {

@@ -340,12 +340,14 @@ ORC_API void orc_mindssc(const float* img, int H, int W, int D, int radius, int 
     float* var = (float*)malloc(sizeof(float) * V);
     mind_patch_ssd(img, H, W, D, radius, dilation, ssd);
     /* :59-60  mind = ssd - min_c ssd ; mind_var = mean_c(mind) = (sequential sum c=0..11) / 12 */
-    float imin = img[0], imax = img[0];
-    for (size_t i = 1; i < V; ++i) { if (img[i] < imin) imin = img[i]; if (img[i] > imax) imax = img[i]; }
+    /* (the image's range only sizes the exact accumulation below; the reference computes none.  fminf / fmaxf skip a NaN voxel; a
+     * non-finite voxel makes some variance NaN and with it the mean, whatever the grids are) */
+    float imin = INFINITY, imax = -INFINITY;
+    for (size_t i = 0; i < V; ++i) { imin = fminf(imin, img[i]); imax = fmaxf(imax, img[i]); }
 #pragma omp parallel for schedule(static)
     for (size_t x = 0; x < V; ++x) {
-        float mn = ssd[x];
-        for (int c = 1; c < 12; ++c) { const float v = ssd[(size_t)c * V + x]; if (v < mn) mn = v; }
+        float mn = ssd[x];       /* torch.min over the channels: a NaN wins (:59) */
+        for (int c = 1; c < 12; ++c) { const float v = ssd[(size_t)c * V + x]; if (v < mn || v != v) mn = v; }
         float mc[12];
         for (int c = 0; c < 12; ++c) { const float m = ssd[(size_t)c * V + x] - mn; ssd[(size_t)c * V + x] = m; mc[c] = m; }
         var[x] = outer_sum_rows(mc, 12, x >= (V / 32) * 32) / 12.0f;
@@ -357,14 +359,18 @@ ORC_API void orc_mindssc(const float* img, int H, int W, int D, int radius, int 
     for (size_t x = 0; x < V; ++x) orc_split_add(&sp, (double)var[x], &a1, &a2, &a3);
     float gmean = (float)((a1 + (a2 + a3)) / (double)V);
     if (g_mean_threads > 0) gmean = orc_torch_sum(var, (int64_t)V, g_mean_threads, g_mean_vec) / (float)V;   /* sum_out(..).div_(numel) */
+    /* :52-53 the shifts are convolutions with one-hot kernels: an infinite voxel meets a zero weight, 0 * Inf = NaN, and the NaN reaches
+     * the mean (here the differences see the voxel itself: an infinite variance, whose sum is Inf under torch's order) */
+    if (isinf(imin) || isinf(imax)) gmean = NAN;
     if (mean_out) *mean_out = gmean;
     const float lo = (float)((double)gmean * 0.001), hi = (float)((double)gmean * 1000.0);
     /* :61-66 clamp, divide, exp(-x), permute */
 #pragma omp parallel for schedule(static)
     for (size_t x = 0; x < V; ++x) {
         float v = var[x];
-        v = v < lo ? lo : v;   /* torch.clamp: min(max(x, lo), hi); NaN propagates */
-        v = v > hi ? hi : v;
+        v = v < lo ? lo : v;   /* torch.clamp: min(max(x, lo), hi); NaN propagates -- from x and from a bound: a NaN mean (any NaN */
+        v = v > hi ? hi : v;   /* or infinite voxel) makes EVERY variance NaN, hence every descriptor value */
+        if (lo != lo || hi != hi) v = NAN;
         for (int j = 0; j < 12; ++j) {
             const float m = ssd[(size_t)MIND_PERM[j] * V + x] / v;
             out[(size_t)j * V + x] = orc_mind_exp(m);
