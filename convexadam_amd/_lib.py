@@ -2,7 +2,8 @@
 
 One table per public header: SIGNATURES (include/convexadam_hip.h), PREP_SIGNATURES (convexadam_prep.h), FIELD_SIGNATURES
 (convexadam_field.h), AFFINE_SIGNATURES (convexadam_affine.h); lib() types all four when it loads the library.  SOFT_SIGNATURES
-(convexadam_soft.h) is typed by soft_lib(), on the first call of convexadam_amd.confidence, as strictly and by name.  Every entry point that
+(convexadam_soft.h) is typed by soft_lib(), on the first call of convexadam_amd.confidence, as strictly and by name, and SIM_SIGNATURES
+(convexadam_sim.h) by sim_lib(), on the first call of convexadam_amd.similarity.  Every entry point that
 takes a stream is entered through call(), every scratch buffer comes from scratch().
 
 The HIP library IS the product: there is no CPU or PyTorch fallback.  If the shared object is
@@ -212,9 +213,17 @@ SOFT_SIGNATURES = {
     "cvx_soft_stats_f32": (_i, [_vp, _i, _vp, _f, _f, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
 }
 
+# include/convexadam_sim.h (typed by sim_lib() below, not at load)
+SIM_SIGNATURES = {
+    "cvx_sim_range_f32": (_i, [_vp, _vp] + _FIELD + [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "cvx_joint_hist_f32": (_i, [_vp, _vp] + _FIELD + [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
+    "cvx_joint_hist_lds_bytes": (_i, [_i, _i]),
+}
+
 _REBUILD = "rebuild with `python -m convexadam_amd.csrc.build`"
 _lib = None
 _soft_typed = None          # the handle soft_lib() has typed SOFT_SIGNATURES on
+_sim_typed = None           # the handle sim_lib() has typed SIM_SIGNATURES on
 _lock = threading.Lock()
 
 
@@ -261,6 +270,15 @@ def soft_lib():
     L = lib()
     if _soft_typed is not L:
         _soft_typed = bind(L, SOFT_SIGNATURES)
+    return L
+
+
+def sim_lib():
+    """lib() with the entry points of include/convexadam_sim.h typed as well, exactly as soft_lib() does it (and for its reason)."""
+    global _sim_typed
+    L = lib()
+    if _sim_typed is not L:
+        _sim_typed = bind(L, SIM_SIGNATURES)
     return L
 
 

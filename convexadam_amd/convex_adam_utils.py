@@ -478,3 +478,6 @@ from .affine import (affine_from_field, affine_to_field, convex_adam_affine, fin
 # the soft reading of the cost volume -- mean, covariance, entropy per coarse cell (no counterpart in the reference): csrc/softstats.hip
 from .confidence import (Confidence, convex_confidence, soft_covariance, soft_displacement, soft_entropy, soft_sigma,  # noqa: E402,F401
                          soft_stats)
+# mutual information of a pair -- fused warp + joint histogram, entropies, MI and NMI (no counterpart in the reference): csrc/simhist.hip
+from .similarity import (RegistrationMI, entropies, joint_histogram, mutual_information,  # noqa: E402,F401
+                         normalized_mutual_information, registration_mi, value_range)
