@@ -12,9 +12,16 @@ field is bit-identical to the CPU oracle's), inputs already resident in HBM.  Wi
 registers its own pairs (no collective on the data path); the timed region is bracketed by
 barrier + synchronize and the slowest rank's time is used: value = N*K / T (weak scaling).
 
-The printed line stays under 8 KB (bench_line): the contract keys, roofline, cpu_baseline, stages_ms, the mode values, the parity verdict and
-one figure per secondary config.  The whole record, every object below included, goes to --extra-out (default bench_extra.json next to
-this script).
+A plain run does what `value` needs and no more: it generates the pair, warms up, times the steps, writes --dump-outputs and prints the
+line with the contract keys, stages_ms and roofline (both read from HIP events the timed steps record themselves).  Everything else below
+-- cpu_baseline and the parity verdicts, the other modes and storage types, configs, batched, the per-kernel figures -- runs after the
+timed steps with --full only (minutes; --no-cpu-baseline / --no-batched leave out its two halves):
+
+    python bench.py --gpus 1 --steps K --warmup W --full
+
+The printed line stays under 8 KB (bench_line): the contract keys, roofline, stages_ms and, with --full, cpu_baseline, the mode values, the
+parity verdict and one figure per secondary config.  With --full the whole record, every object below included, goes to --extra-out
+(default bench_extra.json next to this script).
   roofline     the SSD correlation stage (k_corr_prep + k_corr_fused of one direction, certified-fast arithmetic): algorithmic bytes
                (n^3*v*4 written + 2*C*v*4 read = 273.5 MB) / its mean duration measured with HIP events on the
                launch stream inside the timed region, against 8 TB/s HBM3E peak; `traffic` = HBM bytes per launch
@@ -538,22 +545,37 @@ def secondary_configs(dev):
     return res
 
 
-def main():
+def parse_args(argv=None):
+    """The command line -> namespace, with what --full decides already applied: without it both halves of the secondary work are off
+    (no_cpu_baseline, no_batched) and no side file is written."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-batched", action="store_true", help="skip the secondary measurements (batched pairs, other configs, modes)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run everything else this script measures or checks: the CPU baseline "
+                    "and the parity verdicts, the other modes, precisions and configs, batched pairs, the per-kernel figures (minutes instead of seconds; "
+                    "never part of `value`).  Without it the run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle, the parity block and the drop-in API timing")
+    ap.add_argument("--no-batched", action="store_true", help="with --full: skip the secondary measurements (batched pairs, other configs, modes)")
     ap.add_argument("--adam-mode", default="exact", choices=("exact", "fast"), help="mode of the timed loop: exact = the package default (what `value` "
                     "means); fast = the opt-in throughput arithmetic of the Adam loop (profiling runs; the line then says so in `mode`)")
     ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the field of the last timed step as .npy files under DIR "
                     "(a seeded sample of it and its whole-field moments; see dump_outputs)")
-    ap.add_argument("--extra-out", default=os.path.join(ROOT, "bench_extra.json"), metavar="FILE",
-                    help="where the whole result record goes (every secondary figure; the printed line carries the contract keys); '' = nowhere")
-    a = ap.parse_args()
+    ap.add_argument("--extra-out", default=None, metavar="FILE",
+                    help="where the whole result record goes (every secondary figure; the printed line carries the contract keys); '' = nowhere.  "
+                         "Default: bench_extra.json next to this script with --full, nowhere without (a plain run has no secondary figure to keep)")
+    a = ap.parse_args(argv)
     if a.steps < 1 or a.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not a.full:              # a plain run measures `value` and what the timed steps themselves record (stages_ms, roofline); nothing runs after them
+        a.no_cpu_baseline = a.no_batched = True
+    if a.extra_out is None:
+        a.extra_out = os.path.join(ROOT, "bench_extra.json") if a.full else ""
+    return a
+
+
+def main():
+    a = parse_args()
     global TIMED, TIMED_MODE_NAME
     if a.adam_mode == "fast":
         TIMED, TIMED_MODE_NAME = FAST, "adam_mode=fast (OPT-IN, not the package default; run with --adam-mode fast)"

@@ -1067,6 +1067,38 @@ def test_bench_line_with_two_ranks_on_one_gpu():
     assert "cpu_baseline" not in b and b["roofline"]["frac"] > 0 and b["vs_baseline"] is None
 
 
+def test_plain_bench_run_is_lean(tmp_path):
+    """`bench.py --gpus 1 --steps N --warmup W` without --full, in a fresh process: one JSON line with the contract keys and what the
+    timed steps record themselves (stages_ms, roofline), none of the objects that take runs of their own, no side file, the dumped field
+    where --dump-outputs says, and at most 30 s between start and exit that are not steps: wall clock - (N + W) x ms_per_step."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import time
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    n, w = 3, 1
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(n), "--warmup", str(w), "--dump-outputs", str(tmp_path / "dump")]
+    t0 = time.perf_counter()
+    r = subprocess.run(cmd, cwd=str(tmp_path), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+    wall = time.perf_counter() - t0
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1 and len(lines[0]) < 8192, r.stdout[-2000:]
+    b = json.loads(lines[0])
+    assert b["n_gpus"] == 1 and b["steps"] == n and b["warmup"] == w and b["unit"] == "pairs/s" and b["dtype"] == "f32" and b["higher_is_better"] is True
+    assert abs(b["value"] - 1e3 / b["ms_per_step"]) < 1e-6 * b["value"]
+    assert b["roofline"]["frac"] > 0 and b["stages_ms"]["adam"] > 0 and b["extra"] is None
+    moved = ("cpu_baseline", "parity", "configs", "tolerance_met", "value_exact_mode", "value_fast_mode", "value_at_tolerance", "value_zero_background")
+    assert not [k for k in moved if k in b], sorted(b)
+    assert sorted(os.listdir(tmp_path)) == ["dump"] and sorted(os.listdir(tmp_path / "dump")) == ["displacement_moments.npy", "displacement_sample.npy"]
+    for name in os.listdir(tmp_path / "dump"):                      # 48 MiB: not left behind in pytest's kept directories
+        os.remove(tmp_path / "dump" / name)
+    outside = wall - (n + w) * b["ms_per_step"] * 1e-3
+    print("plain bench run: %.2f s from start to exit, %.2f s of it outside the %d steps" % (wall, outside, n + w))
+    assert outside <= 30.0, (wall, outside)
+
+
 # ---- (5) Euclidean feature transform of the masked path (SURVEY 8(f).2) ------------------------------------------------
 def test_feature_transform_vs_scipy_and_oracle(M, orc):
     """Device EDT indices == scipy.ndimage.distance_transform_edt(return_indices=True) (the call of convex_adam_MIND.py:44),

@@ -473,6 +473,27 @@ def test_bench_line_is_short_strict_json_with_the_contract_keys():
     assert set(b["configs"]) == {"configs[2]", "configs[3]", "configs[4]"} and b["configs"]["configs[2]"]["corr_frac"] > 0
 
 
+def test_bench_plain_run_does_no_secondary_work_and_full_brings_it_back():
+    """bench.py without --full: both halves of the work after the timed steps are off whatever else is passed, and no side file is
+    written unless one is named; --full restores today's defaults, and --no-cpu-baseline / --no-batched still take its halves out."""
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert (a.full, a.no_cpu_baseline, a.no_batched, a.extra_out) == (False, True, True, "")
+    assert (a.gpus, a.steps, a.warmup, a.adam_mode, a.dump_outputs) == (1, 7, 3, "exact", None)
+    a = bench.parse_args(["--no-batched", "--dump-outputs", "d", "--extra-out", "x.json"])
+    assert (a.no_cpu_baseline, a.no_batched, a.extra_out, a.dump_outputs) == (True, True, "x.json", "d")
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "3", "--full"])
+    assert (a.full, a.no_cpu_baseline, a.no_batched) == (True, False, False)
+    assert a.extra_out == os.path.join(ROOT, "bench_extra.json") and (a.steps, a.warmup) == (7, 3)
+    a = bench.parse_args(["--full", "--no-cpu-baseline", "--extra-out", ""])
+    assert (a.no_cpu_baseline, a.no_batched, a.extra_out) == (True, False, "")
+    # the line of a plain run: the contract keys and what the timed steps record, no key of the work that moved
+    res = {"metric": "m", "value": 1.0, "unit": "pairs/s", "n_gpus": 1, "steps": 7, "warmup": 3, "ms_per_step": 1e3, "higher_is_better": True,
+           "dtype": "f32", "roofline": {"frac": 0.2}, "stages_ms": {"adam": 1.0}, "roofline_by_stage": {}}
+    line = bench.bench_line(res, None)
+    assert line == dict({k: v for k, v in res.items() if k != "roofline_by_stage"}, extra=None)
+
+
 def test_bench_dump_outputs_is_a_fixed_sample_under_64_mb(tmp_path):
     """bench.py --dump-outputs: float32 / float64 .npy files, at most 64 MB in all, the same files for the same field."""
     import bench
