@@ -3,8 +3,9 @@
 One table per public header: SIGNATURES (include/convexadam_hip.h), PREP_SIGNATURES (convexadam_prep.h), FIELD_SIGNATURES
 (convexadam_field.h), AFFINE_SIGNATURES (convexadam_affine.h); lib() types all four when it loads the library.  SOFT_SIGNATURES
 (convexadam_soft.h) is typed by soft_lib(), on the first call of convexadam_amd.confidence, as strictly and by name, and SIM_SIGNATURES
-(convexadam_sim.h) by sim_lib(), on the first call of convexadam_amd.similarity.  Every entry point that
-takes a stream is entered through call(), every scratch buffer comes from scratch().
+(convexadam_sim.h) by sim_lib(), on the first call of convexadam_amd.similarity, and SPLINE_SIGNATURES (convexadam_spline.h) by
+spline_lib(), on the first call of convexadam_amd.spline.  Every entry point that takes a stream is entered through call(), every scratch
+buffer comes from scratch().
 
 The HIP library IS the product: there is no CPU or PyTorch fallback.  If the shared object is
 missing (not built) or an operator is called with tensors that do not live on a HIP device, the call
@@ -220,10 +221,18 @@ SIM_SIGNATURES = {
     "cvx_joint_hist_lds_bytes": (_i, [_i, _i]),
 }
 
+# include/convexadam_spline.h (typed by spline_lib() below, not at load)
+SPLINE_SIGNATURES = {
+    "cvx_spline_prefilter_f64": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    "cvx_map_coordinates_cubic_f64": (_i, [_vp] + _FIELD + [_i, _i, _i, _vp, _vp]),
+    "cvx_resample_cubic_f64": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _d, _vp]),
+}
+
 _REBUILD = "rebuild with `python -m convexadam_amd.csrc.build`"
 _lib = None
 _soft_typed = None          # the handle soft_lib() has typed SOFT_SIGNATURES on
 _sim_typed = None           # the handle sim_lib() has typed SIM_SIGNATURES on
+_spline_typed = None        # the handle spline_lib() has typed SPLINE_SIGNATURES on
 _lock = threading.Lock()
 
 
@@ -279,6 +288,15 @@ def sim_lib():
     L = lib()
     if _sim_typed is not L:
         _sim_typed = bind(L, SIM_SIGNATURES)
+    return L
+
+
+def spline_lib():
+    """lib() with the entry points of include/convexadam_spline.h typed as well, exactly as soft_lib() does it (and for its reason)."""
+    global _spline_typed
+    L = lib()
+    if _spline_typed is not L:
+        _spline_typed = bind(L, SPLINE_SIGNATURES)
     return L
 
 

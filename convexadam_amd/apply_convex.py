@@ -1,6 +1,7 @@
 """Mirror of the reference's `src/convexAdam/apply_convex.py::apply_convex` (:13-24) on the HIP device.
 
     apply_convex(disp, moving) -> np.ndarray     warped = scipy.ndimage.map_coordinates(moving, disp + identity, order=1)
+    apply_convex(disp, moving, order=3)          ... order=3 (cubic B-splines, convexadam_amd/spline.py; `--order 3` on the command line)
 
 `disp` is the (H,W,D,3) field convex_adam_pt returns (channel a = displacement along axis a, voxels); `moving` any
 (H,W,D) array, image or tensor.  Like scipy, the interpolation runs in float64; non-tensor inputs of any dtype are converted with
@@ -17,7 +18,11 @@ from ._lib import call, ptr
 from .convex_adam_utils import rescale_displacement_field, validate_image
 
 
-def apply_convex(disp, moving, device=None) -> np.ndarray:
+def apply_convex(disp, moving, device=None, order=1) -> np.ndarray:
+    """order=1: scipy's map_coordinates(order=1), the reference's call; order=3: its order=3 with the same defaults (cubic B-splines:
+    the prefilter and the 64-tap gather of convexadam_amd.spline, float64 on the device); every other order raises ValueError."""
+    if order not in (1, 3):
+        raise ValueError("apply_convex: order must be 1 (linear) or 3 (cubic B-spline), got %r" % (order,))
     # validate_image(img, dtype=float): every non-tensor input (numpy, SimpleITK, nibabel; any integer type) becomes float64
     # (convex_adam_utils.py:268-279), tensors pass through with their dtype
     mov_t = validate_image(moving)
@@ -29,8 +34,12 @@ def apply_convex(disp, moving, device=None) -> np.ndarray:
     m = mov_t.to(dev, torch.float64).contiguous()
     d = disp_t.to(dev, torch.float64).contiguous()
     H, W, D = [int(v) for v in m.shape]
-    out = torch.empty_like(m)
-    call(dev, "cvx_map_coordinates_linear_f64", ptr(m), ptr(d), H, W, D, ptr(out))
+    if order == 3:
+        from .spline import warp_cubic
+        out = warp_cubic(m, d)
+    else:
+        out = torch.empty_like(m)
+        call(dev, "cvx_map_coordinates_linear_f64", ptr(m), ptr(d), H, W, D, ptr(out))
     if not out_dtype.is_floating_point:
         out = torch.trunc(out + torch.where(out > 0, 0.5, -0.5))   # scipy's integer outputs: (type)(t > 0 ? t + 0.5 : t - 0.5), ni_interpolation.c
     return out.to(out_dtype).cpu().numpy()
@@ -64,17 +73,18 @@ def apply_convex_original_moving(disp, moving_image_original, fixed_image_origin
 
 def main(argv=None):
     """python -m convexAdam.apply_convex --input_field disp.nii.gz --input_moving moving.nii.gz --output_warped warped.nii.gz
-    (apply_convex.py:81-97): NIfTI through nibabel when installed, else through the built-in reader / writer."""
+    [--order 3] (apply_convex.py:81-97): NIfTI through nibabel when installed, else through the built-in reader / writer."""
     import argparse
     from . import nifti_io
     ap = argparse.ArgumentParser()
     ap.add_argument("--input_field", required=True, help="input convex displacement field (.nii.gz) full resolution")
     ap.add_argument("--input_moving", required=True, help="input moving scan (.nii.gz)")
     ap.add_argument("--output_warped", required=True, help="output warped scan (.nii.gz)")
+    ap.add_argument("--order", type=int, default=1, choices=(1, 3), help="interpolation order: 1 linear (the reference's), 3 cubic B-spline")
     a = ap.parse_args(argv)
     moving = nifti_io.load_fdata(a.input_moving).astype("float32")
     disp = nifti_io.load_fdata(a.input_field).astype("float32")
-    warped = apply_convex(disp=disp, moving=moving)
+    warped = apply_convex(disp=disp, moving=moving, order=a.order)
     nifti_io.save_image(warped, nifti_io.load_affine(a.input_moving), a.output_warped)
     return 0
 

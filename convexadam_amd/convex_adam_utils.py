@@ -481,3 +481,5 @@ from .confidence import (Confidence, convex_confidence, soft_covariance, soft_di
 # mutual information of a pair -- fused warp + joint histogram, entropies, MI and NMI (no counterpart in the reference): csrc/simhist.hip
 from .similarity import (RegistrationMI, entropies, joint_histogram, mutual_information,  # noqa: E402,F401
                          normalized_mutual_information, registration_mi, value_range)
+# cubic B-spline interpolation -- prefilter, warp and resampling at scipy's order=3 (apply_convex(order=3), resample_device(order=3)): csrc/spline.hip
+from .spline import spline_coefficients, warp_cubic  # noqa: E402,F401

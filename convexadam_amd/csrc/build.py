@@ -11,7 +11,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-SOURCES = ["api.hip", "mind.hip", "mindmarch.hip", "pool.hip", "labelpool.hip", "correlate.hip", "corrbox.hip", "corrfused.hip", "corrcert.hip", "certify.hip", "convex.hip", "adam.hip", "constdiv.hip", "adamfast.hip", "warp.hip", "boxmarch.hip", "boxtile.hip", "metrics.hip", "edt.hip", "surfdist.hip", "pipeline.hip", "tps.hip", "rigid.hip", "rigidreg.hip", "ssim.hip", "geometry.hip", "fieldmean.hip", "cropfield.hip", "ranksum.hip", "prep.hip", "fieldops.hip", "affine.hip", "softstats.hip", "simhist.hip"]
+SOURCES = ["api.hip", "mind.hip", "mindmarch.hip", "pool.hip", "labelpool.hip", "correlate.hip", "corrbox.hip", "corrfused.hip", "corrcert.hip", "certify.hip", "convex.hip", "adam.hip", "constdiv.hip", "adamfast.hip", "warp.hip", "boxmarch.hip", "boxtile.hip", "metrics.hip", "edt.hip", "surfdist.hip", "pipeline.hip", "tps.hip", "rigid.hip", "rigidreg.hip", "ssim.hip", "geometry.hip", "fieldmean.hip", "cropfield.hip", "ranksum.hip", "prep.hip", "fieldops.hip", "affine.hip", "softstats.hip", "simhist.hip", "spline.hip"]
 PER_FILE_FLAGS = {"warp.hip": ["-fno-slp-vectorize"], "adamfast.hip": ["-fno-slp-vectorize"], "boxmarch.hip": ["-fno-slp-vectorize"], "boxtile.hip": ["-fno-slp-vectorize"], "corrbox.hip": ["-fno-slp-vectorize"], "corrfused.hip": ["-fno-slp-vectorize"], "corrcert.hip": ["-fno-slp-vectorize"], "mindmarch.hip": ["-fno-slp-vectorize"], "ssim.hip": ["-fno-slp-vectorize"]}     # see the header of warp.hip
 LIB = os.path.join(HERE, "libconvexadam_hip.so")
 OBJDIR = os.path.join(HERE, "build")
@@ -38,7 +38,7 @@ def build(force=False, verbose=False, jitter=False):
     libconvexadam_hip_jitter.so; select it at run time with CONVEXADAM_HIP_LIB=<path>."""
     objdir, lib = (os.path.join(HERE, "build_jitter"), os.path.join(HERE, "libconvexadam_hip_jitter.so")) if jitter else (OBJDIR, LIB)
     os.makedirs(objdir, exist_ok=True)
-    headers = [os.path.join(HERE, f) for f in sorted(os.listdir(HERE)) if f.endswith(".h")] + [os.path.join(ROOT, "include", "convexadam_hip.h"), os.path.join(ROOT, "include", "convexadam_prep.h"), os.path.join(ROOT, "include", "convexadam_field.h"), os.path.join(ROOT, "include", "convexadam_affine.h"), os.path.join(ROOT, "include", "convexadam_soft.h"), os.path.join(ROOT, "include", "convexadam_sim.h"), os.path.abspath(__file__)]
+    headers = [os.path.join(HERE, f) for f in sorted(os.listdir(HERE)) if f.endswith(".h")] + [os.path.join(ROOT, "include", "convexadam_hip.h"), os.path.join(ROOT, "include", "convexadam_prep.h"), os.path.join(ROOT, "include", "convexadam_field.h"), os.path.join(ROOT, "include", "convexadam_affine.h"), os.path.join(ROOT, "include", "convexadam_soft.h"), os.path.join(ROOT, "include", "convexadam_sim.h"), os.path.join(ROOT, "include", "convexadam_spline.h"), os.path.abspath(__file__)]
     jobs = []
     for src in SOURCES:
         s = os.path.join(HERE, src)

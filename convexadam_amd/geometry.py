@@ -3,7 +3,8 @@ with SimpleITK's resampler before and after a registration (convex_adam_utils.py
 
     grid_of(img)                                   Grid(size, spacing, origin, direction) of anything with SimpleITK's accessors
     index_map(src_grid, out_grid)                  M (3, 3), t (3,): source index (x, y, z) = M @ output index + t
-    resample_device(src, src_grid, out_grid)       ITK-convention linear resampling of a (z, y, x) device tensor onto another grid
+    resample_device(src, src_grid, out_grid)       ITK-convention linear (order=3: cubic B-spline) resampling of a (z, y, x) device tensor
+                                                   onto another grid
     rescale_displacement_field_device(...)         a field on the resampled fixed grid -> the original moving image's grid, axes and voxel
                                                    size and, in the same launch, that image warped by it
     field_mean_device(field, ...)                  sums and count of a field over all voxels, a mask, or a segmentation on its own grid
@@ -63,18 +64,25 @@ def _volume(t, grid, name):
     return t.contiguous(), int(t.dtype == torch.float64)
 
 
-def resample_device(src, src_grid, out_grid, default=0.0):
+def resample_device(src, src_grid, out_grid, default=0.0, order=1):
     """Linear resampling of the (z, y, x) device tensor `src` living on `src_grid` onto `out_grid`, identity transform, `default`
     outside (imageio.resample on the device).  float32 and float64 keep their dtype; integer sources are interpolated in float64 and
-    cast back with round-half-even, like np.rint there."""
+    cast back with round-half-even, like np.rint there.  order=3: cubic B-splines instead (convexadam_amd.spline: the prefilter, then the
+    gather under the same inside rule); every other order raises ValueError."""
+    if order not in (1, 3):
+        raise ValueError("resample_device: order must be 1 (linear) or 3 (cubic B-spline), got %r" % (order,))
     require_device_tensor(src, "src")
     src_grid, out_grid = grid_of(src_grid), grid_of(out_grid)
     s, s64 = _volume(src, src_grid, "src")
     M, t = index_map(src_grid, out_grid)
     sx, sy, sz = src_grid.size
     ox, oy, oz = out_grid.size
-    out = torch.empty((oz, oy, ox), dtype=s.dtype, device=s.device)
-    call(s.device, "cvx_resample_linear_f64", ptr(s), s64, sz, sy, sx, ptr(out), s64, oz, oy, ox, _doubles(M, t), float(default))
+    if order == 3:
+        from .spline import resample_cubic
+        out = resample_cubic(s, (oz, oy, ox), _doubles(M, t), default, out_f64=bool(s64))
+    else:
+        out = torch.empty((oz, oy, ox), dtype=s.dtype, device=s.device)
+        call(s.device, "cvx_resample_linear_f64", ptr(s), s64, sz, sy, sx, ptr(out), s64, oz, oy, ox, _doubles(M, t), float(default))
     if src.dtype in (torch.float32, torch.float64):
         return out
     if src.dtype.is_floating_point:
